@@ -6,13 +6,19 @@ with the HBM-roofline fraction of the dominant kernel and the reference's CPU pa
     python bench.py [--gpus N --steps K --warmup W]          N > 1: this process starts the N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      (the driver's form)
     python bench.py --workload batch1d_f64 | stream | image [--rowband]      the other BASELINE configs as the main line
+    python bench.py --full                                    everything else the benchmark measures and checks (below)
+    python bench.py --dump-outputs DIR                        the last timed step's outputs as DIR/y_<mode>.npy (headline only)
 
 A step = one pass of savgol_apply_batch_f32 over the whole resident batch in EACH of the four boundary
 modes (4 launches of the centre kernel; the POLYNOMIAL one carries its edge rows as extra items).  Inputs are generated in HBM
 before the timed region.  Channels are independent: with N GPUs every rank owns its own 4096 channels
-(weak scaling, no data-path collective); rank 0 prints one JSON line.  At N = 1 that line also carries, under
-"extra", BASELINE configs 1, 3, 4 and the per-GPU slice of config 5, each with its own roofline and CPU baseline
-(--no-extra skips them).
+(weak scaling, no data-path collective); rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (its roofline from the timed launches' own events).
+--full adds what takes runs or checks of its own: the copy / read ceilings of the same buffers, the CPU baselines, parity
+spot checks against the oracle and the reference's own output, the secondary summation modes and, at N = 1, under "extra",
+BASELINE configs 1, 3, 4 and the per-GPU slice of config 5, each with its own roofline and CPU baseline (--no-cpu and
+--no-extra take parts of that back out).
 """
 import argparse
 import json
@@ -31,6 +37,7 @@ from __graft_entry__ import load_package  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 N, M, D = 32, 4, 0
+MODE_NAMES = {0: "polynomial", 1: "reflect", 2: "periodic", 3: "constant"}
 # the dominant kernels of configs 3 / 4 as rocprofv3 names them (profiles/r05_*_kernel_stats.csv)
 STREAM_KERNEL_FMA = "sg_bank_dma_kernel<16,true,32,8,16,1,2,MomTaps<16,2>> (LDS-DMA tiles, 8-tick block moments; SAVGOL_HIP_STREAM_MOMENT=0: tap by tap; SAVGOL_HIP_STREAM_DMA=0: sg_bank_roll_kernel<16,true>)"
 STREAM_KERNEL_REF = "sg_bank_dma_kernel<16,false,...> (SAVGOL_HIP_STREAM_DMA=0: sg_bank_roll_kernel<16,false>)"
@@ -345,6 +352,32 @@ def emit(out):
     except (OSError, AttributeError):
         pass
     print(json.dumps(out), flush=True)
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: every array of one run together (< 64 MB)
+DUMP_SEED = 0x5A17
+
+
+def dump_sample(t, share):
+    """a 2-D device tensor as a host array of at most `share` bytes: whole, or a fixed, seeded sample of its rows (the same rows
+    from run to run for the same shape; both ends of every row kept when a single row alone is over the share)"""
+    rows, cols = t.shape
+    item = t.element_size()
+    keep = min(cols, max(2, share // item))
+    k = min(rows, max(1, share // (keep * item)))
+    idx = np.arange(rows) if k == rows else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, k, replace=False))
+    sub = t[torch.as_tensor(idx, device=t.device)]
+    if keep < cols:
+        sub = torch.cat([sub[:, :keep // 2], sub[:, cols - (keep - keep // 2):]], dim=1)
+    return sub.cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: host array from dump_sample} -> path/<name>.npy (fp32 or fp64, as the timed path wrote it)"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def build_facts(sg):
@@ -1019,7 +1052,7 @@ def run_stream(r):
     bank = sg.StreamBank(S, 16, 2, 1, 1e-3, fma=True)       # SAVGOL_STREAMBANK_FMA; the reference-order bank is timed beside it under "latency"
     # a step is 0.39 ms: W warm-up steps do not bring the memory clocks back up after the set-up phase; a quarter of a second of the same pushes does (R6.13)
     sustain(lambda: bank.push_block(x, T, y))
-    ceil = copy_ceiling(sg, x, y)
+    ceil = copy_ceiling(sg, x, y) if args.full else {}
 
     def step(events):
         e0, e1 = ev(), ev()
@@ -1036,7 +1069,7 @@ def run_stream(r):
                "config": {"workload": f"BASELINE config 3: {S} streams per GPU x {T} ticks per step, n=16, m=2, d=1, dt=1e-3", "sharding": "streams, no collective"},
                "roofline": add_ceiling(with_traffic(roofline(8.0 * S * T, ms, lms, kernel=STREAM_KERNEL_FMA), "r*_stream_block_pmc_summary.json", SOURCES_STREAM), ceil)}
         out.update(r.per_rank_fields(8.0 * S * T))
-        if r.world == 1 and not args.no_extra:
+        if r.world == 1 and args.full and not args.no_extra:
             out["latency"] = bench_stream(sg, args)
             if "cpu_baseline" in out["latency"]:
                 out["cpu_baseline"] = out["latency"]["cpu_baseline"]
@@ -1129,7 +1162,7 @@ def run_image(r):
         Nimg = args.images
         x = torch.empty((Nimg * size, size), dtype=torch.float32, device=dev); sg.synth(x, channel0=r.rank * Nimg * size)
         y = torch.empty_like(x)
-        ceil = copy_ceiling(sg, x, y)
+        ceil = copy_ceiling(sg, x, y) if args.full else {}
 
         def step(events):
             for b in (0, 1, 2):
@@ -1155,7 +1188,7 @@ def run_image(r):
             if args.rowband:
                 pr.pop("rccl_ranks", None)                  # the row-band line reports the exchange's own communicator (extra_top)
             out.update(pr)
-        if r.world == 1 and not args.no_cpu:
+        if r.world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_reference("image")
         emit(out)
     r.finish()
@@ -1167,7 +1200,7 @@ def run_config5(r):
     channels, chunk, length = args.c5_channels, args.c5_chunk, 1 << 22
     x, y, resident, full_out = config5_buffers(sg, channels, chunk, length, r.rank, dev)
     f = sg.Filter(N, M, 2, 1.0, 0)
-    ceil = copy_ceiling(sg, x[:chunk], y[:chunk], reps=3)
+    ceil = copy_ceiling(sg, x[:chunk], y[:chunk], reps=3) if args.full else {}
     # the tolerance config 5 states, in the call (savgol_apply_batch_f64_tol); --f64-exact: the default tap-by-tap path (1e-12) instead
     exact = args.f64_exact
     call_kw = {"flags": 0} if exact else {"rel_tol": C5_TOL}
@@ -1195,7 +1228,7 @@ def run_config5(r):
                                                     "r*_1d_f64_n32_pmc_summary.json" if exact else "r*_1d_f64m_n32_pmc_summary.json"), ceil)}
         out.update(r.per_rank_fields(16.0 * chunk * length))
         out["config"]["call"] = "savgol_apply_batch_f64_ex(flags=0): 1e-12 of the fp64 oracle" if exact else f"savgol_apply_batch_f64_tol(rel_tol={C5_TOL:g}): the bar the config states"
-        if r.world == 1 and not args.no_cpu:
+        if r.world == 1 and args.full and not args.no_cpu:
             from oracle import sgo
             sample = [0, chunk - 1]
             c0 = resident - chunk
@@ -1249,7 +1282,7 @@ def run_headline(r):
     sg.synth(x, channel0=ch0)                               # generated in HBM, never crosses PCIe
     filters = [sg.Filter(N, M, D, 1.0, mode) for mode in modes]
     torch.cuda.synchronize()
-    ceil = copy_ceiling(sg, x, y)                           # the same two buffers, the same process, before the timed region
+    ceil = copy_ceiling(sg, x, y) if args.full else {}      # the same two buffers, the same process, before the timed region
 
     def step(events):
         for f in filters:
@@ -1258,6 +1291,16 @@ def run_headline(r):
             if events is not None:
                 events.append((e0, e1))
     elapsed, events = r.timed_region(step)
+    if r.rank == 0 and args.dump_outputs:
+        # y holds the last step's CONSTANT pass; the step's other three passes are run again on the same buffers, then CONSTANT, which leaves y
+        # as the step left it (the --full legs below read it)
+        share = DUMP_BYTES // len(modes)
+        got = {f"y_{MODE_NAMES[modes[-1]]}": dump_sample(y, share)}
+        for f, mode in zip(filters, modes):
+            f.apply_batch(x, y, ch, length)
+            if mode != modes[-1]:
+                got[f"y_{MODE_NAMES[mode]}"] = dump_sample(y, share)
+        dump_outputs(args.dump_outputs, got)
 
     if r.rank == 0:
         launches_ms = [a.elapsed_time(b) for a, b in events]
@@ -1286,7 +1329,7 @@ def run_headline(r):
         out.update(r.per_rank_fields(alg_bytes))
         if args.total_channels:
             out["scaling"] = "strong"
-        if r.world == 1 and not args.no_cpu:
+        if r.world == 1 and args.full and not args.no_cpu:
             # CPU leg (rank 0, N=1 only): the reference timed on this host + parity spot checks of what was just timed
             # (last mode run = CONSTANT) against the CPU oracle and against the reference's own fp32 output -- the only place bench.py touches oracle/
             out["cpu_baseline"] = cpu_baseline(length)
@@ -1306,7 +1349,7 @@ def run_headline(r):
             d1 = parity_fields(y[sample].cpu().numpy(), refd, refd32, which)
             out["parity_d1"] = {k: v for k, v in d1.items() if k != "reference_fp32_from"}
             assert d1["parity_normwise_vs_fp64_oracle"] < max(1e-6, 1.1 * d1["reference_fp32_own_error_vs_fp64_oracle"])
-        if r.world == 1:
+        if r.world == 1 and args.full:
             # secondary figures, outside the timed region
             L = sg.lib()
             sec = {}
@@ -1329,7 +1372,7 @@ def run_headline(r):
                 sec["bit_identical_mode"]["note"] = ("reference summation order (four chains, separate multiply and add): outputs equal the reference "
                                                      "library's bit for bit")
             out.update(sec)
-        if r.world == 1 and not args.no_extra:
+        if r.world == 1 and args.full and not args.no_extra:
             # PLACEMENT SPREAD (round 5, profiles/EXPERIMENTS.md R5.9): the same launch on a few FRESH buffer pairs inside this process, the timed pair
             # kept alive so that new physical pages back the new ones -- how much of this run's `frac` is where its two 16 GiB buffers happen to
             # sit.  Outside the timed region; `roofline.frac` above is the timed pair's and nothing else.
@@ -1359,8 +1402,12 @@ def main():
     ap.add_argument("--length", type=int, default=1 << 20)
     ap.add_argument("--total-channels", type=int, default=0, help="batch1d: a fixed channel count split over the ranks by savgol_hip_shard_range (uneven shards when it "
                                                                    "does not divide; scaling 'strong') instead of --channels per GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs and the oracle spot checks")
-    ap.add_argument("--no-extra", action="store_true", help="headline only: skip the configs 1/3/4/5 'extra' section")
+    ap.add_argument("--full", action="store_true", help="beside the headline figure: copy / read ceilings, CPU baselines, parity spot checks against the oracle "
+                                                        "and the reference, secondary summation modes, placement spread and (N = 1) the configs 1/3/4/5 'extra' section")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline legs and the oracle spot checks")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the configs 1/3/4/5 'extra' section and the placement spread")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="--workload batch1d: after the timed steps, write the four outputs of the last step as "
+                                                                        "DIR/y_<mode>.npy (fp32; over 48 MiB in all: a fixed, seeded sample of whole channels)")
     ap.add_argument("--workload", choices=["batch1d", "batch1d_f64", "stream", "image"], default="batch1d",
                     help="batch1d = the headline (BASELINE config 2); batch1d_f64 = config 5's per-GPU slice (4096 channels x 2^22 fp64, "
                          "n=32, d=2, POLYNOMIAL, 1024-channel chunks); stream / image = configs 3 / 4")
@@ -1379,6 +1426,10 @@ def main():
     ap.add_argument("--f64-exact", action="store_true", help="--workload batch1d_f64: the default tap-by-tap fp64 path (1e-12 of the oracle) instead of "
                                                             "savgol_apply_batch_f64_tol(rel_tol=1e-6), the tolerance config 5 states")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload != "batch1d":
+        ap.error("--dump-outputs writes the headline's outputs: --workload batch1d only")
 
     # ---- N ranks: start them from here, BEFORE anything in this process touches the GPU (never re-exec after that) ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

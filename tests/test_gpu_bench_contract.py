@@ -6,7 +6,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from tests._util import normwise, same_bits
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +30,7 @@ def run(cmd, env=None):
 
 
 def test_single_gpu_line():
-    d = run([sys.executable, "bench.py", "--channels", "256", "--length", "262144", "--steps", "3", "--warmup", "1"])
+    d = run([sys.executable, "bench.py", "--channels", "256", "--length", "262144", "--steps", "3", "--warmup", "1", "--full"])
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
     assert d["unit"] == "Msamples/s" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["vs_baseline"] is None
     assert set(d["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"} and d["roofline"]["bound"] == "hbm"
@@ -70,6 +73,32 @@ def test_single_gpu_line():
     if "skipped" not in rb:
         assert rb["rccl_ranks"] == 1 and rb["exchange_ms"] > 0 and rb["band_ms"] > 0 and rb["edge_strips_ms"] > 0 and rb["step_ms"] > 0
         assert rb["parity_normwise_vs_fp64_oracle"] < 1e-6
+
+
+def test_plain_line_is_lean_and_dumps_what_it_timed(tmp_path, sg, sgo):
+    """Without --full the line carries the headline and its roofline and nothing that takes runs or checks of its own; --dump-outputs writes
+    the last step's four outputs (whole, at this size), which are the oracle's answer and do not depend on how many steps ran."""
+    import torch
+    ch, length = 8, 65536
+    d = run([sys.executable, "bench.py", "--channels", str(ch), "--length", str(length), "--steps", "3", "--warmup", "1",
+             "--dump-outputs", str(tmp_path / "a")])
+    assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert d["unit"] == "Msamples/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4 * ch * length * 3 / (d["ms_per_step"] * 3 * 1e-3) / 1e6) / d["value"] < 0.01
+    assert not {"cpu_baseline", "extra", "summary", "parity_normwise_vs_fp64_oracle", "plain_65_tap_sum", "bit_identical_mode"} & set(d), sorted(d)
+    assert "copy_frac" not in d["roofline"] and "placement_spread" not in d["roofline"]
+    names = ["y_polynomial", "y_reflect", "y_periodic", "y_constant"]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(n + ".npy" for n in names)
+    x = torch.empty((ch, length), dtype=torch.float32, device="cuda")
+    sg.synth(x)                                                    # bench.py's input, channel 0 on
+    xh = x.cpu().numpy().astype(np.float64)
+    for mode, name in enumerate(names):
+        y = np.load(tmp_path / "a" / (name + ".npy"))
+        assert y.dtype == np.float32 and y.shape == (ch, length), (name, y.dtype, y.shape)
+        assert normwise(y, sgo.Filter(32, 4, 0, 1.0, mode).apply_f64(xh)) < 1e-6, name
+    run([sys.executable, "bench.py", "--channels", str(ch), "--length", str(length), "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")])
+    for name in names:
+        assert same_bits(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))), name
 
 
 def test_exchange_c_fails_loudly_when_it_cannot_come_up():

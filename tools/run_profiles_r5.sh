@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/r5_prof; mkdir -p $O
 # ONLY=stream (or f32 / f64 / image): just that kernel's counter passes (after a change to that kernel's sources)
 if [ -z "$ONLY" ]; then
-python bench.py > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc $?"
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc $?"
 fi
 cd /tmp && export TMPDIR=/tmp
 B=$GRAFT_REPO_ROOT/bench.py
