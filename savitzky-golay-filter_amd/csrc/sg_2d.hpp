@@ -46,13 +46,9 @@ __device__ __forceinline__ f32x2 pk_fold(const f32x2 s, const f32x2 b, const f32
 // instructions fewer per row at n = 7, rank 2 (135 -> 125).
 __device__ __forceinline__ f32x2 pk_middle(const f32x2 lo, const f32x2 hi)
 {
-#ifdef SG_ROLL_PLAIN_MIDDLE
-    return pk_straddle(lo, hi);
-#else
     f32x2 r;
     asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,0]" : "=v"(r) : "v"(lo), "v"(hi));
     return r;
-#endif
 }
 // fix_index (sg_2d.hpp) without branches: the row index is wave-uniform, so this is a handful of SALU selects
 __device__ __forceinline__ int fix_row(int i, int n, bool reflect)

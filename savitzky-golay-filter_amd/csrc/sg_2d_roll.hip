@@ -58,11 +58,7 @@ struct Roll {
     // with HL = 1, 5.15 with HL = 2 (stores on 64-byte boundaries) and 5.22 with HL = 4 (stores on 128-byte lines); the kernel
     // itself gains 8-11 % at n <= 4 with HL = 2 and 7 % at n = 5, 6 with HL = 4; n = 7, 8 and the VALU-bound n >= 9 gain nothing
     // (tools/ab_2d.py, same process)
-#ifdef SG_ROLL_HL_MIN
-    static constexpr int HL = (N + 3) / 4 > SG_ROLL_HL_MIN ? (N + 3) / 4 : SG_ROLL_HL_MIN;
-#else
     static constexpr int HL = N <= 4 ? 2 : (N <= 6 ? 4 : (N + 3) / 4);
-#endif
     static constexpr int OUTL = 64 - 2 * HL;                // lanes whose columns are stored
     static constexpr int SW = 4 * OUTL;                     // stored columns per strip
     static constexpr int NQ = 2 * HL + 1;                   // 16-byte quads a lane reads back per term
@@ -72,22 +68,13 @@ struct Roll {
     // 64 frames, n = 9: 2.41 -> 2.29), nothing or a loss below (tools/ab_2d.py, all builds in one process)
     // (accumulating passes, n >= 9: the output rows they add to are prefetched through a ring of four slots, which wants U to be a
     //  multiple of four: P = 5 at odd half windows)
-#ifdef SG_ROLL_P
-    static constexpr int P = TR > 0 ? TR - 1 : SG_ROLL_P;
-#else
     static constexpr int P = TR > 0 ? TR - 1 : ((ACC && (N & 1) && N < 15) ? 5 : (N >= 6 ? 3 : 1));
-#endif
     static constexpr int U = 2 * N + 1 + P;                 // ring slots = unroll factor of the row loop
     // branch-free row loop (buffer stores whose range check replaces the `if`, whole groups of U rows without an exit test).
     // It paid (+4 % at n=7, +12-15 % at n = 10, 12) while the LDS reads of a row were issued right before their use: the branches
     // made hipcc wait for vmcnt(1) where vmcnt(6) was meant.  With the reads issued a pass early (see roll_item) the plain loop
-    // is as fast or faster at every half window (n=7: 1.96 vs 2.04 ms, n=12: 2.87 vs 3.04), so it is off; the macro keeps the
-    // variant buildable for the next compiler.
-#ifdef SG_ROLL_STRAIGHT
-    static constexpr bool STRAIGHT = TR > 0 || SG_ROLL_STRAIGHT != 0;
-#else
+    // is as fast or faster at every half window (n=7: 1.96 vs 2.04 ms, n=12: 2.87 vs 3.04), so only the tiles are branch-free.
     static constexpr bool STRAIGHT = TR > 0;                // a tile's waits must stay counted: 2N + TR loads are in flight when its first row starts
-#endif
     static constexpr int BUFW = 256 + 8 * HL;               // LDS floats per term row (strip + pad both sides)
     static constexpr int NP = N / 2 + 1;                    // SGPR pairs holding taps 0..N
 };
@@ -105,9 +92,6 @@ struct RollTaps {
 // The additive form's weighted horizontal unit, X-STATIONARY (round 5): one window float, broadcast, times the SGPR pair (a[k], a[k-1]) feeds the
 // output pair (c, c + 1) -- no folded pairs, no v_pk_mov_b32 for the pairs that straddle two aligned registers: 2 (2N + 2) multiply-adds per lane and
 // row instead of 2 (N + 1) + 2 N folds + ~N moves (n = 7: 32 against 39 of the row's 94 vector instructions).  Same idiom as sg_k1d_momenth.hpp.
-#ifndef SG_ROLL_XST
-#define SG_ROLL_XST 1
-#endif
 template <int HALF>
 __device__ __forceinline__ void roll_fma_xb(f32x2 &acc, const f32x2 s, const f32x2 x)
 {
@@ -190,15 +174,11 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
     const bool reflect = job.boundary == SAVGOL2D_BOUNDARY_REFLECT;
     auto load_row = [&](int r) -> f32x4 {                    // rows past the band are clamped re-reads that are never used
         const float *row = in + (long long)fix_row(yb - N + r, job.rows, reflect) * job.in_stride;
-#ifdef SG_ROLL_NT_LOADS                                           // A/B builds: streaming loads (the strip's halo columns then miss L2 for the neighbour)
-        if constexpr (VEC) return __builtin_bit_cast(f32x4, __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(row + c0)));
-#else
         if constexpr (EDGE) {
             const f32x4 q = *reinterpret_cast<const f32x4 *>(row + qcol);
             const float nx = fx_w ? q.w : q.x, nw = fx_x ? q.x : q.w;          // a broadcast lane has nx == nw == the edge float
             return f32x4{nx, fx_b ? nx : (fx_rev ? q.z : q.y), fx_b ? nx : (fx_rev ? q.y : q.z), nw};
         } else if constexpr (VEC) return *reinterpret_cast<const f32x4 *>(row + c0);
-#endif
         else return f32x4{row[ix0], row[ix1], row[ix2], row[ix3]};
     };
     const bool out_lane = lane >= R::HL && lane < 64 - R::HL;
@@ -356,7 +336,7 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
             r[1] = r[1] + f32x2{s2, s3};
             return;
         }
-        if constexpr (SG_ROLL_XST && BOX && NOUT == 1 && t == 0 && TR > 0) {     // tiles only: on the strip walk (n >= 11) the 2N + 2 SGPR pairs cost more than the moves (4-9 % slower)
+        if constexpr (BOX && NOUT == 1 && t == 0 && TR > 0) {     // tiles only: on the strip walk (n >= 11) the 2N + 2 SGPR pairs cost more than the moves (4-9 % slower)
             // window float D + i is tap i - p of output c0 + p and tap i - p - 1 of output c0 + p + 1 (p = 0: r[0], p = 2: r[1]); two chains per
             // output pair (even / odd i), joined below
             f32x2 ch[2][2];
@@ -537,16 +517,11 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
 
 // terms per output the rolling kernel is built for: the taps live in SGPRs (2 * NT * NOUT * (N/2 + 1) pairs), which caps the
 // windows 9..12 at 3 terms and 13..16 at 2 (1 when two outputs share the walk); everything else runs the tile kernel of sg_2d_sep.hip
-// (three outputs -- the Hessian -- share the walk up to n = 9 with one term each: every Hessian frame of order <= 3 is rank 1)
-constexpr int roll_max_terms(int n, int nout) { return nout == 1 ? (n <= 8 ? SEP_MAX_TERMS : (n <= 12 ? 3 : 2)) : nout == 2 ? (n <= 8 ? 3 : 1) : (n <= 3 ? 2 : (n <= 9 ? 1 : 0)); }
+constexpr int roll_max_terms(int n, int nout) { return nout == 1 ? (n <= 8 ? SEP_MAX_TERMS : (n <= 12 ? 3 : 2)) : (n <= 8 ? 3 : 1); }
 // waves per SIMD the register allocation must allow: the row ring alone is (2N+2) x 4 VGPRs
 // (n = 7 and n = 8 with three rows in flight and the two-output form at n = 6, rank 2, spill at 4 waves per SIMD: 300 / 20-108 / 12
 // bytes of scratch; tools/roll_resources.py lists every instantiation)
-#ifdef SG_ROLL_MINWAVES
-constexpr int roll_min_waves(int, int, int) { return SG_ROLL_MINWAVES; }
-#else
-constexpr int roll_min_waves(int n, int nt, int nout) { return n >= 9 ? 2 : ((nt >= 3 && n >= 6) || n == 7 || n == 8 || (n == 6 && nt == 2 && nout == 2) || (nout == 3 && n >= 5) ? 3 : 4); }
-#endif
+constexpr int roll_min_waves(int n, int nt, int nout) { return n >= 9 ? 2 : ((nt >= 3 && n >= 6) || n == 7 || n == 8 || (n == 6 && nt == 2 && nout == 2) ? 3 : 4); }
 
 // TILE form: output rows per tile (0 = this half window keeps the strip walk) and the waves per SIMD its registers must allow.
 // tools/membench_tile2d.hip (profiles/r04_membench_tile2d.txt): the bare tile pattern moves 0.71-0.72 of the roofline at full
@@ -556,118 +531,66 @@ constexpr int roll_min_waves(int n, int nt, int nout) { return n >= 9 ? 2 : ((nt
 // SIMD, and over fresh buffer pairs in one process (tools/placement_2d.py, profiles/r05_2d_tile_rows.txt) 20-row tiles are 1.4-2.4 % faster than 16 at
 // n = 2, 3, 7 (all three boundary modes), 0.3-0.9 % at n = 4, 5, 6; 18: 0.7 %, 22 / 24: 1.6 / 5.5 % SLOWER.  (Round 4's single-placement sample of the old
 // kernel had 20 rows 12 % slower: it crossed 168 registers then.)
-#ifndef SG_ROLL_TILE_ROWS
-#define SG_ROLL_TILE_ROWS 20
-#endif
-// the general one- and two-term forms of one output frame run as tiles too (derivative frames, orders 4-5 of small windows): 12-20 % faster
-// than the walk at n = 2 ... 7 with one term, 12-20 % (n <= 5) / 1-5 % (n = 6, 7) with two (profiles/r04_2d_tile_experiments.txt)
-#ifndef SG_ROLL_TILE_GENERAL
-#define SG_ROLL_TILE_GENERAL 1
-#endif
-// additive form, half windows 8 .. 12 (A/B builds override).  End of round 5, after the x-stationary horizontal unit had freed 2N + 3 register pairs
+constexpr int ROLL_TILE_ROWS = 20;
+// The general one- and two-term forms of one output frame run as tiles too (derivative frames, orders 4-5 of small windows): 12-20 % faster
+// than the walk at n = 2 ... 7 with one term, 12-20 % (n <= 5) / 1-5 % (n = 6, 7) with two (profiles/r04_2d_tile_experiments.txt).
+// Additive form, half windows 8 .. 12.  End of round 5, after the x-stationary horizontal unit had freed 2N + 3 register pairs
 // (tools/placement_2d.py, 32 frames of 4096^2, ms over six buffer pairs; profiles/r05_2d_tile_rows.txt): n = 8: 10 rows 0.900, 14 rows 0.862, 16 rows 0.889;
 // n = 9: 10 / 12 / 14 rows 0.992 / 0.967 / 0.949; n = 10: 8 / 10 / 12 rows 1.073 / 1.017 / 1.016; n = 11, 12: 8-12-row tiles 1.38-1.62 against the walk's
 // 1.27 / 1.30 at THREE waves per SIMD (67-127 spilled registers).  Two waves per SIMD with taller tiles at n <= 10 (round 6): n = 7 28 / 32 rows 1.68 against
 // 1.585, n = 8 20 / 24 rows 1.95 / 1.81 against 1.64, n = 9 24 rows 1.85-1.87 against 1.82-1.86, n = 10 24 / 28 / 32 rows 1.95-1.96 against 1.99-2.02: left alone
-#ifndef SG_ROLL_TR8
-#define SG_ROLL_TR8 14
-#endif
-#ifndef SG_ROLL_TR9
-#define SG_ROLL_TR9 14
-#endif
-#ifndef SG_ROLL_TR10
-#define SG_ROLL_TR10 10     /* round 6: 12 rows spill 4 registers now that nothing else does; 10 rows were level (1.017 against 1.016 ms) */
-#endif
 // Half windows 11 .. 16 at TWO waves per SIMD (256 registers): the taller the tile, the fewer halo rows per output row, up to what the registers hold
 // (4 (TR + 2N) + ~45; 20 rows spill at n = 16, 18 at n = 14).  64 frames of 4096^2, ms, tools/ab_2d.py (profiles/r06_2d_tiles_n11_16.txt):
 //   n = 11: walk 2.47, 12 rows 2.28-2.35, 16: 2.13, 20: 2.08, 22 / 24: 2.10        n = 12: walk 2.55, 12: 2.38-2.43, 16: 2.24, 20: 2.17-2.19, 22: 2.20, 24: 2.17 (spills)
 //   n = 13: walk 2.78, 8: 2.95, 12: 2.64, 14: 2.56, 16: 2.52, 18: 2.46             n = 14: walk 2.84, 12: 2.91, 14: 2.80, 16: 2.68, 18: 3.10 (spills)
 //   n = 15: walk 3.12, 8: 2.97-3.03, 12: 2.72-2.78, 14: 2.74, 16: 2.61, 18: 2.52, 20: 2.60      n = 16: walk 3.11-3.18, 12: 2.93-2.97, 14: 2.80, 16: 2.88, 18: 2.74, 20: 2.80 (spills)
-#ifndef SG_ROLL_TR11
-#define SG_ROLL_TR11 20
-#endif
-#ifndef SG_ROLL_TR12
-#define SG_ROLL_TR12 20
-#endif
-#ifndef SG_ROLL_TRG11
-#define SG_ROLL_TRG11 0          /* A/B builds: one-term general form (derivative frames), tile rows for every half window 11 .. 16 (0 = the table in roll_tile_rows) */
-#endif
-// one-term general form (derivative frames), half windows 8 .. 10, d = (0,2), 64 frames, ms: three waves per SIMD with 12 / 10 / 10 rows (rounds 4-5) 1.67 / 1.88 / 1.95;
+// One-term general form (derivative frames), half windows 8 .. 10, d = (0,2), 64 frames, ms: three waves per SIMD with 12 / 10 / 10 rows (rounds 4-5) 1.67 / 1.88 / 1.95;
 // TWO waves per SIMD: 16 rows 1.63 / 1.71 / 1.80, 20 rows 1.56 / 1.67 / 1.70-1.73, 24 rows 1.53 / 1.66 / 1.72, 28 rows 1.52 / 1.65 / 1.71
-#ifndef SG_ROLL_TRG8
-#define SG_ROLL_TRG8 24
-#endif
-#ifndef SG_ROLL_TRG9
-#define SG_ROLL_TRG9 24
-#endif
-#ifndef SG_ROLL_TRG10
-#define SG_ROLL_TRG10 20
-#endif
-#ifndef SG_ROLL_TRN2T2
-#define SG_ROLL_TRN2T2 0         /* A/B builds: the fused two-output form with TWO terms per frame (gradient of order 3, 4), half windows <= 8: tile rows (0 = the table in roll_tile_rows) */
-#endif
-#ifndef SG_ROLL_TRN2
-#define SG_ROLL_TRN2 0           /* A/B builds: the fused two-output form (gradient) with one term per frame, tile rows for every half window >= 8 (0 = the table in roll_tile_rows) */
-#endif
-#ifndef SG_ROLL_W2G_FROM
-#define SG_ROLL_W2G_FROM 8       /* the one-term general form runs two waves per SIMD from this half window on */
-#endif
-#ifndef SG_ROLL_TR13
-#define SG_ROLL_TR13 0           // A/B builds: tile rows for every half window 13 .. 16 (0 = the table in roll_tile_rows)
-#endif
 constexpr int roll_tile_rows(int n, int nt, int nout, bool box)
 {
-    if (box && nt == 2 && nout == 1 && n <= 7) return SG_ROLL_TILE_ROWS;
+    if (box && nt == 2 && nout == 1 && n <= 7) return ROLL_TILE_ROWS;
     // half window 8: 16 + 16 rows do not fit three waves per SIMD, 10 + 16 do (with 20 bytes of scratch): 6.92 vs 7.61 ms per 256 frames
     // (12 rows 6.93, 8 rows 7.21; profiles/r04_2d_tile_experiments.txt)
-    if (box && nt == 2 && nout == 1 && n == 8) return SG_ROLL_TR8;
-    if (SG_ROLL_TILE_GENERAL && !box && nout == 1 && nt == 1 && n == 8) return SG_ROLL_TRG8;
+    if (box && nt == 2 && nout == 1 && n == 8) return 14;
+    if (!box && nout == 1 && nt == 1 && n == 8) return 24;
     // half windows 9, 10 (64 frames, ms, tile vs walk): n = 9 additive 1.97 vs 2.25, one term 1.85 vs 2.09 (10 rows; 8 rows 2.05 / 1.95);
     // n = 10 additive 2.14 vs 2.31 (8 rows; 10 spill: 2.16), one term 1.91 vs 2.13 (10 rows, 20 bytes of scratch; 8 rows 2.04)
-    if (box && nt == 2 && nout == 1 && (n == 9 || n == 10)) return n == 9 ? SG_ROLL_TR9 : SG_ROLL_TR10;
-    if (box && nt == 2 && nout == 1 && (n == 11 || n == 12)) return n == 11 ? SG_ROLL_TR11 : SG_ROLL_TR12;
-    if (box && nt == 2 && nout == 1 && n >= 13) return SG_ROLL_TR13 ? SG_ROLL_TR13 : (n == 14 ? 16 : 18);
-    if (SG_ROLL_TILE_GENERAL && !box && nout == 1 && nt == 1 && (n == 9 || n == 10)) return n == 9 ? SG_ROLL_TRG9 : SG_ROLL_TRG10;
+    // (additive n = 10, round 6: 12 rows spill 4 registers now that nothing else does; 10 rows were level, 1.017 against 1.016 ms)
+    if (box && nt == 2 && nout == 1 && (n == 9 || n == 10)) return n == 9 ? 14 : 10;
+    if (box && nt == 2 && nout == 1 && (n == 11 || n == 12)) return 20;
+    if (box && nt == 2 && nout == 1 && n >= 13) return n == 14 ? 16 : 18;
+    if (!box && nout == 1 && nt == 1 && (n == 9 || n == 10)) return n == 9 ? 24 : 20;
     // one-term general form (derivative frames d = (0,1), (1,0), (0,2), ...) at two waves per SIMD, d = (0,2), 64 frames, ms (profiles/r06_2d_tiles_n11_16.txt):
     // n = 11: walk 2.03, 16 rows 1.84, 20 rows 1.76; 12: 2.05 / 1.91 / 1.85; 13: 2.16 / 2.03 / 1.97; 14: 2.26 / 2.12 / 2.07; 15: 2.30-2.32, 12 / 14 / 16 rows 2.46 / 2.33 / 2.30
     // (20 spill); 16: 2.31-2.36, 12 / 14 / 16 rows 2.57 / 2.41 / 2.46: the walk stays at 15 and 16
-    if (SG_ROLL_TILE_GENERAL && !box && nout == 1 && nt == 1 && n >= 11) return SG_ROLL_TRG11 ? SG_ROLL_TRG11 : (n <= 14 ? 20 : 0);
-    if (SG_ROLL_TILE_GENERAL && !box && nout == 1 && nt <= 2 && n <= 7) return SG_ROLL_TILE_ROWS;
-    // the fused two- / three-output forms with one term per frame (gradient of order <= 2, Hessian of order <= 3): the three Hessian frames
-    // of 64 x 4096^2 at n = 7 in 3.54 ms instead of 4.02 (2 waves per SIMD: 178 registers)
-    if (SG_ROLL_TILE_GENERAL && !box && nout >= 2 && nt == 1 && n <= 7) return SG_ROLL_TILE_ROWS;
+    if (!box && nout == 1 && nt == 1 && n >= 11) return n <= 14 ? 20 : 0;
+    if (!box && nout == 1 && nt <= 2 && n <= 7) return ROLL_TILE_ROWS;
+    // the fused two-output form with one term per frame (gradient of order <= 2).  Measured when a three-output (Hessian) form still shared
+    // this path: its three frames of 64 x 4096^2 at n = 7 in 3.54 ms instead of 4.02 (2 waves per SIMD: 178 registers)
+    if (!box && nout == 2 && nt == 1 && n <= 7) return ROLL_TILE_ROWS;
     // two terms per frame (the gradient of an order-3 or -4 filter -- the usual cubic), 64 frames, ms, walk / 16-row / 20-row tiles (tools/ab_2d_gradient.py --order 3; the
     // tile's frames are the walk's bits): n = 2: 2.26 / 2.10 / 2.41; 3: 2.71 / 2.13 / 2.17; 5: 3.08 / 2.64 / 2.79; 7: 3.63 / 3.45 / 3.46; 8: 4.20 / 4.17 / 3.87
-    if (SG_ROLL_TILE_GENERAL && !box && nout == 2 && nt == 2 && n <= 8) return SG_ROLL_TRN2T2 ? SG_ROLL_TRN2T2 : (n == 8 ? 20 : 16);
+    if (!box && nout == 2 && nt == 2 && n <= 8) return n == 8 ? 20 : 16;
     // the same form at half windows 8 .. 12 (gradient of order <= 2, 64 frames, ms, tools/ab_2d_gradient.py; the tile's frames are the walk's bits):
     // n = 8: walk 2.71, 16 rows 2.51, 20 rows 2.63; 9: 3.16 / 2.73 / 2.75; 10: 3.11 / 2.91 / 2.93; 11: 3.54 / 3.19 / 3.22; 12: 3.51 / 3.21 / 3.42 (spills)
-    if (SG_ROLL_TILE_GENERAL && !box && nout == 2 && nt == 1 && n >= 8) return SG_ROLL_TRN2 ? SG_ROLL_TRN2 : (n <= 12 ? 16 : 0);
+    if (!box && nout == 2 && nt == 1 && n >= 8) return n <= 12 ? 16 : 0;
     return 0;
 }
-#ifndef SG_ROLL_TILE_WAVES
-#define SG_ROLL_TILE_WAVES 3
-#endif
-// (the general two-term form at n = 6, 7 spills 36-52 bytes at 3 waves per SIMD)
-#ifndef SG_ROLL_W2_FROM
-#define SG_ROLL_W2_FROM 11       /* tiles of half windows >= this run at TWO waves per SIMD (256 registers: taller tiles) */
-#endif
+// three waves per SIMD, two (256 registers: taller tiles) for the two-output form, the general two-term form from n = 6 (it spills 36-52 bytes
+// at 3 waves per SIMD at n = 6, 7), the one-term general form from n = 8 and every tile from n = 11
 constexpr int roll_tile_waves(int n, int nt = 2, bool box = true, int nout = 1)
 {
-    return (nout >= 2 || (!box && nt == 2 && n >= 6) || (!box && nt == 1 && n >= SG_ROLL_W2G_FROM) || n >= SG_ROLL_W2_FROM) ? 2 : SG_ROLL_TILE_WAVES;
+    return (nout >= 2 || (!box && nt == 2 && n >= 6) || (!box && nt == 1 && n >= 8) || n >= 11) ? 2 : 3;
 }
 
-// waves per block: the waves of a block walk neighbouring strips row for row, so a block's loads of one row step are one
-// contiguous run of the frame row
-#ifndef SG_ROLL_WPB
-#define SG_ROLL_WPB 4
-#endif
+// waves per block: 4 on the strip walk -- the waves of a block walk neighbouring strips row for row, so a block's loads of one row step are
+// one contiguous run of the frame row
 // (tile form: 2 -- a block retires when its slowest wave does, and 2 of a frame row's 18 strips are edge strips; 64 / 256 frames of
 //  4096^2 at n = 7: 1 wave 1.65 / 6.85 ms, 2 waves 1.61 / 6.58, 4 waves 1.69 / 6.84, 8 waves 2.05 / 7.85)
-#ifndef SG_ROLL_TILE_WPB
-#define SG_ROLL_TILE_WPB 2
-#endif
-constexpr int roll_wpb(int n, int tr = 0) { (void)n; return tr > 0 ? SG_ROLL_TILE_WPB : SG_ROLL_WPB; }
+constexpr int roll_wpb(int n, int tr = 0) { (void)n; return tr > 0 ? 2 : 4; }
 
+// out2 is never read: it served a three-output form that is gone.  It stays because dropping it would change the kernarg layout, and
+// with it the code of every rolling kernel; the host passes nullptr.
 template <int N, int NT, int NOUT, bool BOX, bool ACC, int TR = 0>
 __global__ __launch_bounds__(64 * roll_wpb(N, TR), TR > 0 ? roll_tile_waves(N, NT, BOX, NOUT) : roll_min_waves(N, NT, NOUT)) void sg2d_rolling_kernel(const Job2D job, const RollTaps<N, NT, NOUT> taps, float *const out1, float *const out2,
                                                            unsigned strips, unsigned bands, int band_rows, unsigned total_items, int aligned)
@@ -681,7 +604,7 @@ __global__ __launch_bounds__(64 * roll_wpb(N, TR), TR > 0 ? roll_tile_waves(N, N
     // one item per wave by default (the loop runs once), or persistent waves striding over the items; blocks that share an XCD
     // (blockIdx % 8) take neighbouring items (halo columns meet in L2)
     const unsigned nblk = gridDim.x;
-    // bit 3: blocks in launch order (A/B: SAVGOL_HIP_ROLL_XCD=0).  Bits 8..: blocks per XCD CHUNK -- chunks are dealt to the XCDs round robin, so the eight
+    // bit 3: blocks in launch order (no launch sets it today).  Bits 8..: blocks per XCD CHUNK -- chunks are dealt to the XCDs round robin, so the eight
     // fronts stay within eight chunks of each other; 0 = every XCD sweeps one contiguous eighth of the launch (rounds 3-5)
     unsigned blk = blockIdx.x;
     if (!(aligned & 8)) {
@@ -704,16 +627,12 @@ __global__ __launch_bounds__(64 * roll_wpb(N, TR), TR > 0 ? roll_tile_waves(N, N
     for (unsigned item = blk * WPB + (unsigned)wv; item < total_items; item += (TR > 0 ? 0xffffffffu - item : nwaves)) {
         const unsigned strip = item % strips, ib = item / strips;
         const unsigned band = ib % bands, img = ib / bands;
-#ifdef SG_ROLL_SKIP_EDGE_STRIPS                                   // timing experiment only (wrong frames): what do the frame-edge strips cost?
-        if (strip == 0 || strip + 1 == strips) continue;
-#endif
         const int yb = (int)band * band_rows;
         const int nout = job.rows - yb < band_rows ? job.rows - yb : band_rows;
         const float *in = job.in + (long long)img * job.in_pitch;
         float *outs[NOUT];
         outs[0] = job.out + (long long)img * job.out_pitch;
         if constexpr (NOUT > 1) outs[1] = out1 + (long long)img * job.out_pitch;
-        if constexpr (NOUT > 2) outs[2] = out2 + (long long)img * job.out_pitch;
         const int sx = (int)strip * R::SW;
         // fast variant: all 256 input columns inside the frame, all SW output columns stored, 16-byte aligned rows
         if ((aligned & 3) == 3 && sx - 4 * R::HL >= 0 && sx - 4 * R::HL + 256 <= job.cols && sx >= xlo && sx + R::SW <= xhi)
@@ -801,18 +720,18 @@ static bool fill_box_taps(RollTaps<N, 2, 1> &taps, const float *factors, float s
 }
 
 template <int N, int NT, int NOUT, bool BOX, bool ACC = false, int TR = 0>
-static int launch_roll_kernel(const Job2D &job, const RollTaps<N, NT, NOUT> &taps, float *out1, float *out2, unsigned images, int cu_count, hipStream_t st)
+static int launch_roll_kernel(const Job2D &job, const RollTaps<N, NT, NOUT> &taps, float *out1, unsigned images, int cu_count, hipStream_t st)
 {
     typedef Roll<N> R;
     int aligned = 0;
     if (job.in_stride % 4 == 0 && job.in_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.in) & 15u) == 0) aligned |= 1;
     if (job.out_stride % 4 == 0 && job.out_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.out) & 15u) == 0 &&
-        (NOUT < 2 || (reinterpret_cast<uintptr_t>(out1) & 15u) == 0) && (NOUT < 3 || (reinterpret_cast<uintptr_t>(out2) & 15u) == 0) &&
+        (NOUT < 2 || (reinterpret_cast<uintptr_t>(out1) & 15u) == 0) &&
         (long long)job.rows * job.out_stride * 4 < 0x7fffff00ll) aligned |= 2;       // the store descriptor holds a 31-bit byte count
     if (TR > 0 && job.cols % 4 == 0 && job.cols >= 32) aligned |= 4;
     if constexpr (TR > 0) {
         // frames a tile kernel cannot take on vector loads alone (odd strides, unaligned bases, cols % 4 != 0, narrower than 32 columns): the strip walk
-        if ((aligned & 7) != 7) return launch_roll_kernel<N, NT, NOUT, BOX, ACC, 0>(job, taps, out1, out2, images, cu_count, st);
+        if ((aligned & 7) != 7) return launch_roll_kernel<N, NT, NOUT, BOX, ACC, 0>(job, taps, out1, images, cu_count, st);
     }
     const unsigned strips = (unsigned)((job.cols + R::SW - 1) / R::SW);
     static int per_cu = 0;                                   // resident blocks per CU of this instantiation
@@ -867,14 +786,21 @@ static int launch_roll_kernel(const Job2D &job, const RollTaps<N, NT, NOUT> &tap
             if (chunk_items % WPB == 0 && chunk_items / WPB < (1u << 22) && chunk_items / WPB * 8u <= grid) aligned_launch |= (int)((unsigned)(chunk_items / WPB) << 8);
         }
         hipLaunchKernelGGL((sg2d_rolling_kernel<N, NT, NOUT, BOX, ACC, TR>), dim3(grid), dim3(64 * WPB), lds, st, part, taps,
-                           out1 ? out1 + (long long)i0 * job.out_pitch : nullptr, out2 ? out2 + (long long)i0 * job.out_pitch : nullptr, strips, bands,
+                           out1 ? out1 + (long long)i0 * job.out_pitch : nullptr, nullptr, strips, bands,
                            band_rows, (unsigned)total, aligned_launch);
     }
     return 0;
 }
 
+// SAVGOL_HIP_ROLL_TILE=0: every half window on the strip walk of rounds 1-3 (A/B runs)
+static bool roll_tiles_on()
+{
+    static const bool on = [] { const char *e = getenv("SAVGOL_HIP_ROLL_TILE"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
 template <int N, int NT, int NOUT>
-static int launch_roll(const Job2D &job, const float *const (&factors)[NOUT], const float (&scale)[NOUT], float *out1, float *out2, unsigned images,
+static int launch_roll(const Job2D &job, const float *const (&factors)[NOUT], const float (&scale)[NOUT], float *out1, unsigned images,
                        int cu_count, hipStream_t st)
 {
     if (job.accumulate) {
@@ -883,7 +809,7 @@ static int launch_roll(const Job2D &job, const float *const (&factors)[NOUT], co
             RollTaps<N, NT, 1> taps;
             memset(&taps, 0, sizeof(taps));
             if (!fill_taps<N, NT, 1>(taps, 0, factors[0], scale[0])) return 1;
-            return launch_roll_kernel<N, NT, 1, false, true>(job, taps, out1, out2, images, cu_count, st);
+            return launch_roll_kernel<N, NT, 1, false, true>(job, taps, out1, images, cu_count, st);
         } else return 1;
     }
     if constexpr (NT == 2 && NOUT == 1) {
@@ -892,11 +818,9 @@ static int launch_roll(const Job2D &job, const float *const (&factors)[NOUT], co
         if (fill_box_taps<N>(box, factors[0], scale[0])) {
             constexpr int TR = roll_tile_rows(N, 2, 1, true);
             if constexpr (TR > 0) {
-                // SAVGOL_HIP_ROLL_TILE=0: the strip walk of rounds 1-3 (A/B runs)
-                static const int tile_env = [] { const char *e = getenv("SAVGOL_HIP_ROLL_TILE"); return e ? atoi(e) : 1; }();
-                if (tile_env != 0) return launch_roll_kernel<N, 2, 1, true, false, TR>(job, box, out1, out2, images, cu_count, st);
+                if (roll_tiles_on()) return launch_roll_kernel<N, 2, 1, true, false, TR>(job, box, out1, images, cu_count, st);
             }
-            return launch_roll_kernel<N, 2, 1, true>(job, box, out1, out2, images, cu_count, st);
+            return launch_roll_kernel<N, 2, 1, true>(job, box, out1, images, cu_count, st);
         }
     }
     RollTaps<N, NT, NOUT> taps;
@@ -905,10 +829,9 @@ static int launch_roll(const Job2D &job, const float *const (&factors)[NOUT], co
         if (!fill_taps<N, NT, NOUT>(taps, o, factors[o], scale[o])) return 1;
     constexpr int TRG = roll_tile_rows(N, NT, NOUT, false);
     if constexpr (TRG > 0) {
-        static const int tile_env = [] { const char *e = getenv("SAVGOL_HIP_ROLL_TILE"); return e ? atoi(e) : 1; }();
-        if (tile_env != 0) return launch_roll_kernel<N, NT, NOUT, false, false, TRG>(job, taps, out1, out2, images, cu_count, st);
+        if (roll_tiles_on()) return launch_roll_kernel<N, NT, NOUT, false, false, TRG>(job, taps, out1, images, cu_count, st);
     }
-    return launch_roll_kernel<N, NT, NOUT, false>(job, taps, out1, out2, images, cu_count, st);
+    return launch_roll_kernel<N, NT, NOUT, false>(job, taps, out1, images, cu_count, st);
 }
 
 template <int N, int NT>
@@ -917,7 +840,7 @@ static int dispatch_roll(int n, int terms, const Job2D &job, const float *factor
     if (n == N && terms == NT) {
         const float *const f1[1] = {factors};
         const float s1[1] = {scale};
-        return launch_roll<N, NT, 1>(job, f1, s1, nullptr, nullptr, images, cu_count, st);
+        return launch_roll<N, NT, 1>(job, f1, s1, nullptr, images, cu_count, st);
     }
     if constexpr (NT < roll_max_terms(N, 1)) return dispatch_roll<N, NT + 1>(n, terms, job, factors, scale, images, cu_count, st);
     else if constexpr (N < SEP_ROLL_MAX_N) return dispatch_roll<N + 1, 1>(n, terms, job, factors, scale, images, cu_count, st);
@@ -932,7 +855,7 @@ static int dispatch_roll2(int n, int terms, const Job2D &job, const float *f0, f
     if (n == N && terms == NT) {
         const float *const ff[2] = {f0, f1};
         const float ss[2] = {s0, s1};
-        return launch_roll<N, NT, 2>(job, ff, ss, out1, nullptr, images, cu_count, st);
+        return launch_roll<N, NT, 2>(job, ff, ss, out1, images, cu_count, st);
     }
     if constexpr (NT < roll_max_terms(N, 2)) return dispatch_roll2<N, NT + 1>(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st);
     else if constexpr (N < SEP_ROLL_MAX_N) return dispatch_roll2<N + 1, 1>(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st);

@@ -520,7 +520,7 @@ int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out
 // reaches outputs that are not stored), so the result is the reference's, bit for bit, as before.
 // ------------------------------------------------------------------------------------------------
 constexpr size_t PIPE_MIN_LENGTH = (size_t)1 << 23;       // below this the plain path is as fast
-constexpr size_t PIPE_CHUNK_DEFAULT = (size_t)1 << 22;    // 16 MB of samples per chunk (SAVGOL_HIP_PIPE_CHUNK_LOG2 overrides: tuning)
+constexpr size_t PIPE_CHUNK = (size_t)1 << 22;            // 16 MB of samples per chunk
 constexpr int    PIPE_HALO = 32;                          // >= any half window, multiple of 4
 
 struct PipeStreams { hipStream_t up = nullptr, down = nullptr; };
@@ -557,7 +557,6 @@ int host_apply_pipelined(const char *who, DeviceCtx *ctx, const SavgolFilter *f,
     const int shift = (variant == VALID) ? n : 0;
     const float dt_inv = dt_inverse(f);
 
-    constexpr size_t PIPE_CHUNK = PIPE_CHUNK_DEFAULT;
     const size_t lo = PIPE_HALO, hi = L - PIPE_HALO;                       // centre outputs [lo, hi) go through the chunks
     const size_t nchunks = (hi - lo + PIPE_CHUNK - 1) / PIPE_CHUNK;
     std::vector<hipEvent_t> done(nchunks, nullptr);
@@ -824,7 +823,7 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter, const void *d_
         job.in_pitch = (long long)in_channel_pitch; job.out_pitch = (long long)out_channel_pitch;
         job.in_stride = (long long)in_stride; job.out_stride = (long long)out_stride;
         job.length = (unsigned)count;
-        const unsigned TW = 64u * (unsigned)SG_VPL_NARROW * 4u;
+        const unsigned TW = 64u * (unsigned)sg::VPL_NARROW * 4u;
         job.tiles_per_channel = (unsigned)((count + TW - 1) / TW);
         sg::division_magic(job.tiles_per_channel, &job.tpc_magic, &job.tpc_shift);
         job.dt_inv = dt_inverse(filter);

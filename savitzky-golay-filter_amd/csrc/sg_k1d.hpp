@@ -57,28 +57,17 @@ __device__ __forceinline__ void   vset(double2 &v, int e, double x) { if (e == 0
 __device__ __forceinline__ float  fma_t(float a, float b, float c)    { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
-// streamed-once data: nontemporal loads/stores (SG_NT=0 falls back to the default cache policy)
-#ifndef SG_NT
-#define SG_NT 1
-#endif
+// streamed-once data: nontemporal loads/stores
 template <typename VT> __device__ __forceinline__ VT ld_stream(const VT *p)
 {
     static_assert(sizeof(VT) == 16, "16-byte vectors only");
-#if SG_NT
     const u32x4 raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
     return __builtin_bit_cast(VT, raw);
-#else
-    return *p;
-#endif
 }
 template <typename VT> __device__ __forceinline__ void st_stream(VT *p, const VT &v)
 {
     static_assert(sizeof(VT) == 16, "16-byte vectors only");
-#if SG_NT
     __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), reinterpret_cast<u32x4 *>(p));
-#else
-    *p = v;
-#endif
 }
 
 // index remap of the padded boundary modes (reference get_padded_sample, savgolFilter.c:452-476)
@@ -98,11 +87,6 @@ __device__ __forceinline__ int remap_index(int i, int L, int mode, bool &zero)
     return i;
 }
 
-// half windows from which the fp32 inner products keep two partial sums per output (below: one chain of <= 2N+1 <= 7 terms)
-#ifndef SG_CHAIN_SPLIT_MIN_N
-#define SG_CHAIN_SPLIT_MIN_N 4
-#endif
-
 template <typename T, int N, int V = vectors_per_lane(sizeof(T), N)>
 struct K1D {
     typedef typename V16<T>::type VT;
@@ -121,7 +105,7 @@ struct K1D {
 #ifndef SG_K1D_WAVES
 #define SG_K1D_WAVES 4
 #endif
-    static constexpr int WAVES = SG_K1D_WAVES;               // waves per block, each with its own slab (A/B builds of one kernel family override; the host counts blocks of 4 tiles)
+    static constexpr int WAVES = SG_K1D_WAVES;               // waves per block, each with its own slab (sg_k1d_momenth.hip sets 2; the host counts blocks of 4 tiles)
     // waves per SIMD the register allocation must allow (the LDS slabs allow as many blocks per CU)
     // (fp64 fits 128 VGPRs since its taps moved to SGPRs, but A/B'd in one process the 168-VGPR schedule is 2.5 % faster)
     // (the 12 / 16 KiB tiles hold 3 / 2 blocks per CU in LDS: asking for more only caps the registers for nothing)
@@ -189,7 +173,8 @@ struct Conv<float, N, V> {
     // poly_order <= 6, derivative <= 2 as a multiple of the reference's own error (profiles/r04_fp32_chains.txt): one chain 1.5-3.6,
     // two halves 1.6-4.0, even/odd 0.8-1.8, three round robin 0.7-1.1, four round robin (the reference's split, fused) 0.8-1.0.
     // Cost of three: R more accumulator registers and R packed adds per lane (+3 % instructions at n = 32, time within noise).
-    static constexpr int CH = N >= SG_CHAIN_SPLIT_MIN_N ? 3 : 1;
+    // From half window 4 on; below, one chain of <= 2N+1 <= 7 terms.
+    static constexpr int CH = N >= 4 ? 3 : 1;
     // all accumulator pairs fed by the input pair that starts at window index I
     template <int I, int J = 0>
     static __device__ __forceinline__ void feed(f32x2 (&A)[CH][K::R / 2], const f32x2 (&W)[33], const f32x2 x)
@@ -247,11 +232,7 @@ struct Conv<double, N, V> {
         if constexpr (Rr < K::R) {
             constexpr int k = I - Rr - K::OFF;
             if constexpr (k >= 0 && k <= N) acc[Rr] = __builtin_fma(taps.wd[k], x, acc[Rr]);
-#ifdef SG_F64_HALF_ADDS    // timing experiment only (wrong results): the instruction mix of the symmetric-tap fold, 32 adds + 33 multiply-adds
-            else if constexpr (k > N && k <= 2 * N) acc[Rr] = acc[Rr] + xs;
-#else
             else if constexpr (k > N && k <= 2 * N) acc[Rr] = __builtin_fma(taps.wd[2 * N - k], xs, acc[Rr]);
-#endif
             feed<I, Rr + 1>(acc, taps, x, xs);
         }
     }
@@ -649,9 +630,9 @@ __global__ __launch_bounds__(64 * SG_K1D_WAVES, (K1D<T, N, V>::MIN_WAVES)) void 
 // and two dense scratch frames).  Everything between staging and store is the dense kernel's (Conv<float, N>, same slab).
 // ---------------------------------------------------------------------------------------------
 template <int N>
-__global__ __launch_bounds__(64 * SG_K1D_WAVES, (K1D<float, N, SG_VPL_NARROW>::MIN_WAVES)) void sg1d_strided_kernel(const JobStrided job, const Taps taps)
+__global__ __launch_bounds__(64 * SG_K1D_WAVES, (K1D<float, N, VPL_NARROW>::MIN_WAVES)) void sg1d_strided_kernel(const JobStrided job, const Taps taps)
 {
-    typedef K1D<float, N, SG_VPL_NARROW> K;
+    typedef K1D<float, N, VPL_NARROW> K;
     constexpr int R = K::R, TW = K::TW, NA = K::NA, VPL = K::VPL;
     __shared__ __attribute__((aligned(16))) char smem[K::WAVES * K::SLAB];
     const int lane = threadIdx.x & 63;
@@ -707,7 +688,7 @@ __global__ __launch_bounds__(64 * SG_K1D_WAVES, (K1D<float, N, SG_VPL_NARROW>::M
     wave_lds_sync();
 
     float acc[R];
-    Conv<float, N, SG_VPL_NARROW>::run(slab + 16 * (lane * (VPL + 1)), taps, acc);
+    Conv<float, N, VPL_NARROW>::run(slab + 16 * (lane * (VPL + 1)), taps, acc);
     if (job.flags & JOB_SCALE) {
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] *= job.dt_inv;

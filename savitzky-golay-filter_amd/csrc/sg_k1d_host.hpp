@@ -26,33 +26,12 @@ struct alignas(8) Taps { union { float w[SAVGOL_MAX_WINDOW + 1]; double wd[(SAVG
 //     fp32 n = 13..18: 12 vectors (12 KiB tiles) instead: 2-6 % faster (n = 13: 5.75 -> 5.41 ms, n = 18: 5.72 -> 5.61 over eight
 //     placements), 1-2 % slower at n = 20, 4-6 % at n = 21, 23; fp64 n >= 26: 12 is 3-4 % slower than 8, 16 level (+-1.5 %) with 8.
 //   fp32 n >= 24 (block moments) is laid out for 32 outputs per lane: 8 either way.
-#ifndef SG_VPL_F32_WIDE
-#define SG_VPL_F32_WIDE 8          /* fp32, half_window >= 24; A/B builds override this */
-#endif
-#ifndef SG_VPL_NARROW
-#define SG_VPL_NARROW 8            /* the narrow tile of every other kernel; A/B builds override this */
-#endif
-constexpr int vectors_per_lane(size_t elem_size, int half_window)
-{
-    return (elem_size == 4 && half_window >= 24) ? SG_VPL_F32_WIDE : SG_VPL_NARROW;
-}
-#ifndef SG_WIDE_F32_MAX16
-#define SG_WIDE_F32_MAX16 12         /* last fp32 half window with 16-vector wide tiles (A/B builds override these three) */
-#endif
-#ifndef SG_WIDE_F32_MAX12
-#define SG_WIDE_F32_MAX12 18         /* ... with 12-vector wide tiles above that */
-#endif
-#ifndef SG_WIDE_F64_MAX16
-#define SG_WIDE_F64_MAX16 24         /* last fp64 half window with 16-vector wide tiles */
-#endif
+constexpr int VPL_NARROW = 8;
+constexpr int vectors_per_lane(size_t, int) { return VPL_NARROW; }
 constexpr int wide_vectors_per_lane(size_t elem_size, int half_window)
 {
-#ifdef SG_VPL_NO_WIDE
-    return vectors_per_lane(elem_size, half_window);                    /* A/B builds */
-#else
-    if (elem_size == 4 && half_window > SG_WIDE_F32_MAX16 && half_window <= SG_WIDE_F32_MAX12) return 12;
-    return (elem_size == 8 ? half_window <= SG_WIDE_F64_MAX16 : half_window <= SG_WIDE_F32_MAX16) ? 16 : vectors_per_lane(elem_size, half_window);
-#endif
+    if (elem_size == 4 && half_window > 12 && half_window <= 18) return 12;
+    return (elem_size == 8 ? half_window <= 24 : half_window <= 12) ? 16 : vectors_per_lane(elem_size, half_window);
 }
 // Tiles one launch may hold: the tile kernels run one tile per wave and four waves per 256-thread block, and HIP rejects a launch
 // whose gridDim.x * blockDim.x reaches 2^32 (hip_runtime_api.h), i.e. 2^24 blocks.  Bigger jobs (tens of millions of short

@@ -33,9 +33,7 @@ struct SavgolStreamBank {
 namespace sg {
 
 constexpr int STREAM_ROLL_MAX_N = 32;   // the rolling block-push kernel covers every half window ...
-#ifndef STREAM_RING_MAX_N
-#define STREAM_RING_MAX_N 16             // ... sample ring (tick loop unrolled 2n+4 times) up to here, accumulator ring above
-#endif
+constexpr int STREAM_RING_MAX_N = 16;   // ... sample ring (tick loop unrolled 2n+4 times) up to here, accumulator ring above
 
 // sg_stream_roll.hip: `ticks` pushes of every stream in one launch, outputs only (the caller updates the ring).
 // 0 = launched, 1 = not covered (ticks >= 2^31): use the LDS-tiled kernel of sg_stream.hip.

@@ -30,16 +30,6 @@
 
 namespace sg {
 
-#ifndef SG_DMA_WPB
-#define SG_DMA_WPB 4                                         // waves per block (independent: only how waves are dealt to CUs and how LDS is carved)
-#endif
-#ifndef SG_DMA_STORE_AUX
-#define SG_DMA_STORE_AUX 2                                   // cache policy bits of the output stores: 2 = nontemporal (written once, never read by this launch:
-                                                             // 0.392 against 0.412 ms on one box, profiles/r05_stream_dma.txt; nontemporal row LOADS lose 30 %: the halo rows are re-read)
-#endif
-#ifndef SG_DMA_LOAD_NT
-#define SG_DMA_LOAD_NT 0
-#endif
 #ifndef SG_DMA_MAX_N
 #define SG_DMA_MAX_N 32
 #endif
@@ -50,15 +40,6 @@ template <int N, int TR_> struct DmaShape {
     static constexpr int ROWS = TR + 2 * N, NI = ROWS / 2, RB = 512, SLAB = ROWS * RB;
     static_assert(TR % 2 == 0, "a DMA instruction moves two rows");
 };
-// defaults (A/B'd on config 3's shape, profiles/r05_stream_dma.txt)
-#ifndef SG_DMA_TR
-#define SG_DMA_TR 32
-#endif
-#ifndef SG_DMA_PAIRS
-#define SG_DMA_PAIRS 12                                      // row pairs (KiB) of LDS ring per wave = how far the row loads run ahead of the arithmetic
-                                                             // (8 / 12 / 16 / 24: FMA bank 0.401 / 0.401 / 0.405 / 0.479 ms, bit-exact bank sustained 0.551 / 0.545-0.555 /
-                                                             //  0.579-0.592 / 0.710 on one box: a shallow ring leaves LDS for the waves the bit-exact arithmetic needs)
-#endif
 
 template <int K> __device__ __forceinline__ void wait_vm()
 {
@@ -71,13 +52,8 @@ template <int K> __device__ __forceinline__ void wait_vm()
 __device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_dst)
 {
     unsigned keep;
-#if SG_DMA_LOAD_NT
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#else
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#endif
 }
 
 // vmcnt bookkeeping, all at compile time.  The wave's vector-memory queue, in issue order: the DP DMAs of the prologue, then per step j
@@ -227,9 +203,6 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
                 constexpr int m = mlo + decltype(ic)::value, k = r - m;
                 // two chains (even taps, odd taps), one v_pk_fma_f32 per tap: bank_roll_item's fast form, bit for bit -- or ONE chain in the
                 // reference's order (taller tiles fit the registers; each term rounds once where the reference rounds twice)
-#ifdef SG_DMA_SKIP_TAPS           // timing experiment only (wrong results): how much of a tile's time the multiply-adds are (profiles/EXPERIMENTS.md R5.8)
-                if constexpr (k >= CH && k >= N - SG_DMA_SKIP_TAPS && k <= N + SG_DMA_SKIP_TAPS) return true;
-#endif
                 if constexpr (k < CH) acc[k][m] = pk_mul_sgpr<k>(taps.w[0], x);
                 else pk_fma_sgpr<(k & 1)>(acc[(k & 1) % CH][m], taps.w[k >> 1], x);
                 return true;
@@ -269,7 +242,9 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
             const f32x2 y = (MOM > 0 || FMA) ? __builtin_elementwise_fma(a, f32x2{job.dt_inv, job.dt_inv}, backdt) : a * f32x2{job.dt_inv, job.dt_inv};
             float *orow = job.out + (size_t)(tt < (long long)job.ticks ? tt : 0) * job.streams;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(orow, 0, has_out ? row_bytes : 0, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)voff, 0, SG_DMA_STORE_AUX);
+            // cache policy 2 = nontemporal: written once, never read by this launch (0.392 against 0.412 ms on one box, profiles/r05_stream_dma.txt;
+            // nontemporal row LOADS lose 30 %: the halo rows are re-read)
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)voff, 0, 2);
         }
     };
     // Step g consumes pair g (already in xa, xb), after it has waited for pair g + 1 and issued its LDS reads (their latency hides behind
@@ -379,37 +354,18 @@ template <int N, bool FMA, int TRT, int WPB, int DPR, int FCH = 2>
 template <int N, bool FMA>
 static int launch_bank_dma_shape(const float *center, const BankJob &job, hipStream_t st)
 {
-#ifdef SG_DMA_EXPERIMENT        // A/B build: tile height and waves per block picked per process (tools/experiments.sh stream_dma)
-    static const int tr = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA_TR"); return e ? atoi(e) : SG_DMA_TR; }();
-    static const int wpb = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA_WPB"); return e ? atoi(e) : SG_DMA_WPB; }();
-    static const int dp = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA_PAIRS"); return e ? atoi(e) : SG_DMA_PAIRS; }();
-    static const int fch = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA_CHAINS"); return e ? atoi(e) : 2; }();
-#define SG_DMA_TRY(T, W, P) if (tr == T && wpb == W && dp == P && fch == 2) return launch_bank_dma<N, FMA, T, W, P, 2>(center, job, st);
-#define SG_DMA_TRY1(T, W, P) if (tr == T && wpb == W && dp == P && fch == 1) return launch_bank_dma<N, FMA, T, W, P, 1>(center, job, st);
-#if SG_DMA_EXPERIMENT == 2      // the short list (several half windows in one build)
-    SG_DMA_TRY(32, 4, 12) SG_DMA_TRY(32, 8, 12) SG_DMA_TRY(32, 8, 16) SG_DMA_TRY(32, 4, 16) SG_DMA_TRY(32, 8, 8) SG_DMA_TRY(32, 16, 8)
-#else
-    SG_DMA_TRY(32, 4, 24) SG_DMA_TRY(32, 4, 32) SG_DMA_TRY(32, 2, 24) SG_DMA_TRY(32, 2, 32) SG_DMA_TRY(32, 8, 12) SG_DMA_TRY(32, 8, 16)
-    SG_DMA_TRY(32, 4, 16) SG_DMA_TRY(32, 4, 8) SG_DMA_TRY(32, 4, 12) SG_DMA_TRY(32, 8, 8) SG_DMA_TRY(64, 4, 16) SG_DMA_TRY(64, 4, 8) SG_DMA_TRY(64, 4, 12)
-    SG_DMA_TRY(48, 4, 8) SG_DMA_TRY(48, 4, 12) SG_DMA_TRY(96, 4, 12) SG_DMA_TRY(64, 8, 8) SG_DMA_TRY(64, 2, 12) SG_DMA_TRY(128, 4, 12)
-    SG_DMA_TRY1(32, 4, 8) SG_DMA_TRY1(32, 4, 12) SG_DMA_TRY1(64, 4, 8) SG_DMA_TRY1(64, 4, 12) SG_DMA_TRY1(64, 4, 16) SG_DMA_TRY1(96, 4, 12) SG_DMA_TRY1(64, 8, 8)
-    SG_DMA_TRY1(48, 4, 12) SG_DMA_TRY1(128, 4, 12) SG_DMA_TRY1(64, 2, 12)
-#endif
-#undef SG_DMA_TRY1
-#undef SG_DMA_TRY
-#endif
     // (waves per block, ring pairs) by half window and bank -- interleaved A/B on config 3's shape (profiles/r05_stream_shapes_ab.txt): light tiles run
     // best on fewer, deeper waves -- fused bank n = 8: (8, 12) 0.387 against (4, 12) 0.414 ms; bit-exact bank n = 8: (4, 16) 0.364 against 0.387.  The whole
     // library before / after this table, both banks: n = 4 / 6 / 8 2.5-6.5 % faster, fused n = 11 8.6 %, n = 2 and 10 level; the bit-exact bank from n = 11
     // (66 instructions per output pair at n = 16) keeps (4, 12): (8, 8) and (4, 16) measured 1-3 % slower there
-#ifndef SG_DMA_FLAT_SHAPES        // (A/B builds: every tile on the default shape)
-    if constexpr (SG_DMA_WPB == 4 && SG_DMA_PAIRS == 12 && SG_DMA_TR == 32) {
-        if constexpr (N <= 5) return launch_bank_dma<N, FMA, 32, 4, 16>(center, job, st);
-        else if constexpr (N <= 11 && FMA) return launch_bank_dma<N, FMA, 32, 8, 12>(center, job, st);
-        else if constexpr (N <= 10) return launch_bank_dma<N, FMA, 32, 4, 16>(center, job, st);
-    }
-#endif
-    return launch_bank_dma<N, FMA, SG_DMA_TR, SG_DMA_WPB, SG_DMA_PAIRS>(center, job, st);
+    if constexpr (N <= 5) return launch_bank_dma<N, FMA, 32, 4, 16>(center, job, st);
+    else if constexpr (N <= 11 && FMA) return launch_bank_dma<N, FMA, 32, 8, 12>(center, job, st);
+    else if constexpr (N <= 10) return launch_bank_dma<N, FMA, 32, 4, 16>(center, job, st);
+    // every other tile: 32 ticks, 4 waves per block (only how waves are dealt to CUs and how LDS is carved), 12 row pairs (KiB) of LDS ring per wave =
+    // how far the row loads run ahead of the arithmetic (A/B'd on config 3's shape, profiles/r05_stream_dma.txt -- 8 / 12 / 16 / 24 pairs: FMA bank
+    // 0.401 / 0.401 / 0.405 / 0.479 ms, bit-exact bank sustained 0.551 / 0.545-0.555 / 0.579-0.592 / 0.710 on one box: a shallow ring leaves LDS for
+    // the waves the bit-exact arithmetic needs)
+    return launch_bank_dma<N, FMA, 32, 4, 12>(center, job, st);
 }
 
 template <int N>
@@ -439,17 +395,12 @@ int SG_DMA_FN(int n, int fma, const float *center, const BankJob &job, int /*cu_
 }
 
 #else      // SG_DMA_MOM_BUILD: the third object, block-moment tiles of the fused bank
-#ifndef SG_DMA_MOM_WPB
-#define SG_DMA_MOM_WPB 8                                     // (waves per block, ring pairs) of the block-moment tiles: with a third of the arithmetic gone the tiles
-#define SG_DMA_MOM_PAIRS 16                                  // want FEWER resident waves with deeper rings -- 8 waves per CU, 16 KiB in flight each (R5.9)
-#endif
-#ifndef SG_DMA_MOM_TR
-#define SG_DMA_MOM_TR SG_DMA_TR                              // output ticks per block-moment tile
-#endif
-
-template <int N, int M, int TRT, int WPB, int DPR>
+template <int N, int M>
 static int launch_bank_dma_mom(const StreamMomentFit &fit, const float *center, BankJob job, hipStream_t st)
 {
+    // tiles of 32 ticks, (waves per block, ring pairs) = (8, 16): with a third of the arithmetic gone the block-moment tiles want FEWER resident
+    // waves with deeper rings -- 8 waves per CU, 16 KiB in flight each (R5.9)
+    constexpr int TRT = 32, WPB = 8, DPR = 16;
     typedef DmaShape<N, TRT> D;
     typedef MomGeom<N> G;
     MomTaps<N, M> taps;
@@ -493,35 +444,15 @@ static int launch_bank_dma_mom(const StreamMomentFit &fit, const float *center, 
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-template <int N, int M>
-static int launch_bank_dma_mom_shape(const StreamMomentFit &fit, const float *center, const BankJob &job, hipStream_t st)
-{
-#ifdef SG_DMA_EXPERIMENT        // A/B build: waves per block and ring depth picked per process
-    static const int tr = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA_TR"); return e ? atoi(e) : SG_DMA_MOM_TR; }();
-    static const int wpb = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA_WPB"); return e ? atoi(e) : SG_DMA_MOM_WPB; }();
-    static const int dp = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA_PAIRS"); return e ? atoi(e) : SG_DMA_MOM_PAIRS; }();
-#define SG_DMA_TRY(T, W, P) if (tr == T && wpb == W && dp == P) return launch_bank_dma_mom<N, M, T, W, P>(fit, center, job, st);
-    SG_DMA_TRY(32, 8, 16) SG_DMA_TRY(32, 8, 12) SG_DMA_TRY(32, 4, 16)
-    SG_DMA_TRY(48, 8, 16) SG_DMA_TRY(64, 8, 16) SG_DMA_TRY(64, 8, 12) SG_DMA_TRY(64, 8, 20) SG_DMA_TRY(64, 4, 16) SG_DMA_TRY(64, 4, 24) SG_DMA_TRY(64, 4, 32)
-    SG_DMA_TRY(96, 8, 16) SG_DMA_TRY(128, 8, 16) SG_DMA_TRY(128, 4, 24)
-#undef SG_DMA_TRY
-#endif
-    return launch_bank_dma_mom<N, M, SG_DMA_MOM_TR, SG_DMA_MOM_WPB, SG_DMA_MOM_PAIRS>(fit, center, job, st);
-}
-
-#ifndef SG_DMA_MOM_MIN_N
-#define SG_DMA_MOM_MIN_N STREAM_MOMENT_MIN_N
-#define SG_DMA_MOM_MAX_N STREAM_MOMENT_MAX_N
-#endif
 template <int N>
 static int dispatch_bank_dma_mom(int n, const StreamMomentFit &fit, const float *center, const BankJob &job, hipStream_t st)
 {
     if (n == N) {
-        if (fit.terms == 1) return launch_bank_dma_mom_shape<N, 1>(fit, center, job, st);
-        if (fit.terms == 2) return launch_bank_dma_mom_shape<N, 2>(fit, center, job, st);
-        return launch_bank_dma_mom_shape<N, 3>(fit, center, job, st);
+        if (fit.terms == 1) return launch_bank_dma_mom<N, 1>(fit, center, job, st);
+        if (fit.terms == 2) return launch_bank_dma_mom<N, 2>(fit, center, job, st);
+        return launch_bank_dma_mom<N, 3>(fit, center, job, st);
     }
-    if constexpr (N < SG_DMA_MOM_MAX_N) return dispatch_bank_dma_mom<N + 1>(n, fit, center, job, st);
+    if constexpr (N < STREAM_MOMENT_MAX_N) return dispatch_bank_dma_mom<N + 1>(n, fit, center, job, st);
     else return 1;
 }
 
@@ -530,7 +461,7 @@ static int dispatch_bank_dma_mom(int n, const StreamMomentFit &fit, const float 
 int sg_bank_dma_launch_mom(int n, const float *center, const BankJob &job, int /*cu_count*/, hipStream_t st)
 {
     static const int env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
-    if (!env || n < SG_DMA_MOM_MIN_N || n > SG_DMA_MOM_MAX_N) return 1;
+    if (!env || n < STREAM_MOMENT_MIN_N || n > STREAM_MOMENT_MAX_N) return 1;
     if (job.streams % 128 != 0 || job.streams * 4 >= 0x7fffff00ull) return 1;
     if (((reinterpret_cast<uintptr_t>(job.samples) | reinterpret_cast<uintptr_t>(job.out) | reinterpret_cast<uintptr_t>(job.ring)) & 15u) != 0) return 1;
     if (job.ticks < 64) return 1;
@@ -540,7 +471,7 @@ int sg_bank_dma_launch_mom(int n, const float *center, const BankJob &job, int /
     // reference's fp32 taps (<= 3e-7 of the largest) shows in them -- 1.4e-6 of the oracle where the tap-by-tap tiles are at 0.7e-6 and the reference's
     // own loop at 0.6e-6 (tools/offset_probe_1d.py, R6.16).  Those banks keep the tap-by-tap tiles (7 % slower); config 3's taps are linear.
     if (job.centre && fit.terms >= 3) return 1;
-    return dispatch_bank_dma_mom<SG_DMA_MOM_MIN_N>(n, fit, center, job, st);
+    return dispatch_bank_dma_mom<STREAM_MOMENT_MIN_N>(n, fit, center, job, st);
 }
 
 #endif

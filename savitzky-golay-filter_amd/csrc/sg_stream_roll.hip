@@ -155,11 +155,7 @@ __device__ __forceinline__ void bank_accroll_item(const BankJob &job, const SRol
     // ring by 30-45 % and why more rows "ahead" made them slower.)
     // The loop is unrolled UA rows deep (hipcc drains every memory operation at the back edge: once per UA rows).
     // (ring depth x resident blocks swept in tools/r3/exp32.sh: four rows at full occupancy; eight from n = 28, +7 % at n = 32)
-#ifdef SG_SROLL_PA
-    constexpr int PA = SG_SROLL_PA, UA = N <= 24 ? 16 : 8;
-#else
     constexpr int PA = N >= 28 ? 8 : 4, UA = N <= 24 ? 16 : 8;
-#endif
     static_assert(UA % PA == 0, "slot = row % PA must carry over from one group of UA rows to the next");
     f32x2 ahead[PA];
 #pragma unroll
@@ -222,26 +218,18 @@ __device__ __forceinline__ void bank_accroll_item(const BankJob &job, const SRol
 // G strips x (TR + 2N) rows does).  Rows and stores go through range-checked buffer descriptors (streams beyond the bank read 0 and
 // store nothing; a row without an output selects an empty descriptor), so there is no branch between the first load and the last store
 // and hipcc's vmcnt waits stay counted.
-#ifndef SG_STREAM_TILE_ROWS
-#define SG_STREAM_TILE_ROWS 16
-#endif
-#ifndef SG_STREAM_TILE_WPB
-#define SG_STREAM_TILE_WPB 2
-#endif
-
-#ifndef SG_STREAM_TILE_SPL
-#define SG_STREAM_TILE_SPL 4                                 // streams per lane: 4 = one 16-byte load per row, 2 = one 8-byte load
-#endif
+// Tiles of 16 tick rows, 2 waves per block.
+constexpr int STREAM_TILE_ROWS = 16, STREAM_TILE_WPB = 2;
 template <int N, bool FMA>
-__global__ __launch_bounds__(64 * SG_STREAM_TILE_WPB, 2) void sg_bank_tile_kernel(const BankJob job, const SRollTaps<N> taps, const TileGeom geo)
+__global__ __launch_bounds__(64 * STREAM_TILE_WPB, 2) void sg_bank_tile_kernel(const BankJob job, const SRollTaps<N> taps, const TileGeom geo)
 {
     typedef SRoll<N> R;
-    constexpr int TR = SG_STREAM_TILE_ROWS, ROWS = TR + 2 * N, SPL = SG_STREAM_TILE_SPL, NP = SPL / 2;
+    constexpr int TR = STREAM_TILE_ROWS, ROWS = TR + 2 * N, NP = 2;        // NP: stream pairs of a lane's 16-byte quad
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned nblk = gridDim.x;
     const unsigned blk = (job.aligned & 2) ? blockIdx.x : (blockIdx.x & 7u) * (nblk >> 3) + (blockIdx.x >> 3);
-    const unsigned long long t = (unsigned long long)blk * SG_STREAM_TILE_WPB + (unsigned)wv;
+    const unsigned long long t = (unsigned long long)blk * STREAM_TILE_WPB + (unsigned)wv;
     if (t >= geo.total) return;
     // tile order: groups of `group` neighbouring strips; inside a group band after band, strips fastest
     const unsigned long long per_group = (unsigned long long)geo.group * geo.bands;
@@ -251,7 +239,7 @@ __global__ __launch_bounds__(64 * SG_STREAM_TILE_WPB, 2) void sg_bank_tile_kerne
     const unsigned band = (unsigned)(rem / gs), strip = grp * geo.group + (unsigned)(rem % gs);
     if (band >= geo.bands) return;                                       // the last group is narrower: its tail of the t range is empty
     const size_t t0 = (size_t)band * TR;
-    const unsigned voff = (strip * (64u * SPL) + (unsigned)SPL * (unsigned)lane) * 4u;     // byte offset of this lane's streams in a row
+    const unsigned voff = (strip * 256u + 4u * (unsigned)lane) * 4u;      // byte offset of this lane's streams in a row
     const int row_bytes = (int)(job.streams * 4);
 
     struct Row { f32x2 p[NP]; };
@@ -262,13 +250,9 @@ __global__ __launch_bounds__(64 * SG_STREAM_TILE_WPB, 2) void sg_bank_tile_kerne
         slot = slot < 0 ? slot + R::WS : slot;
         const float *row = h >= 0 ? job.samples + (size_t)h * job.streams : job.ring + (size_t)slot * job.streams;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, row_bytes, 0x00020000);
+        const f32x4 q = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
         Row o;
-        if constexpr (SPL == 4) {
-            const f32x4 q = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
-            o.p[0] = f32x2{q.x, q.y}; o.p[1] = f32x2{q.z, q.w};
-        } else {
-            o.p[0] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, 0, 0));
-        }
+        o.p[0] = f32x2{q.x, q.y}; o.p[1] = f32x2{q.z, q.w};
         return o;
     };
     Row win[ROWS];
@@ -316,13 +300,8 @@ __global__ __launch_bounds__(64 * SG_STREAM_TILE_WPB, 2) void sg_bank_tile_kerne
         const f32x2 s = f32x2{job.dt_inv, job.dt_inv};
         float *orow = job.out + (tt < job.ticks ? tt : 0) * job.streams;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(orow, 0, has_out ? row_bytes : 0, 0x00020000);
-        if constexpr (SPL == 4) {
-            const f32x2 y0 = a[0] * s, y1 = a[1] * s;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{y0.x, y0.y, y1.x, y1.y}), rs, (int)voff, 0, 0);
-        } else {
-            const f32x2 y0 = a[0] * s;
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y0), rs, (int)voff, 0, 0);
-        }
+        const f32x2 y0 = a[0] * s, y1 = a[1] * s;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{y0.x, y0.y, y1.x, y1.y}), rs, (int)voff, 0, 0);
         return true;
     });
 }
@@ -334,7 +313,7 @@ __global__ __launch_bounds__(256) void sg_bank_roll_kernel(const BankJob job, co
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // persistent waves; the 4 waves of a block take adjacent strips (2 KB contiguous per tick row)
     const unsigned nblk = gridDim.x;
-    const unsigned blk = (job.aligned & 2) ? blockIdx.x : (blockIdx.x & 7u) * (nblk >> 3) + (blockIdx.x >> 3);      // bit 1: launch order (A/B: SAVGOL_HIP_STREAM_XCD=0)
+    const unsigned blk = (job.aligned & 2) ? blockIdx.x : (blockIdx.x & 7u) * (nblk >> 3) + (blockIdx.x >> 3);      // bit 1: launch order (launch_bank_roll always sets it)
     const unsigned long long total = (unsigned long long)job.strips * job.bands;
     for (unsigned long long item = (unsigned long long)blk * 4u + (unsigned)wv; item < total; item += (unsigned long long)nblk * 4u) {
         const unsigned strip = (unsigned)(item % job.strips), band = (unsigned)(item / job.strips);
@@ -375,20 +354,20 @@ static int launch_bank_roll(const float *center, BankJob job, int cu_count, hipS
         // the tile form: rows of whole 16-byte quads (the buffer range check works on whole accesses), rows < 2 GiB, at least two tiles of ticks
         const bool quads = job.streams % 4 == 0 && job.streams * 4 < 0x7fffff00ull &&
                            ((reinterpret_cast<uintptr_t>(job.samples) | reinterpret_cast<uintptr_t>(job.out) | reinterpret_cast<uintptr_t>(job.ring)) & 15u) == 0;
-        if (quads && job.ticks >= 2 * SG_STREAM_TILE_ROWS) {
+        if (quads && job.ticks >= 2 * STREAM_TILE_ROWS) {
             TileGeom geo;
-            geo.strips = (unsigned)((job.streams + 64 * SG_STREAM_TILE_SPL - 1) / (64 * SG_STREAM_TILE_SPL));
-            geo.bands = (unsigned)((job.ticks + SG_STREAM_TILE_ROWS - 1) / SG_STREAM_TILE_ROWS);
+            geo.strips = (unsigned)((job.streams + 255) / 256);
+            geo.bands = (unsigned)((job.ticks + STREAM_TILE_ROWS - 1) / STREAM_TILE_ROWS);
             // strips per group: (TR + 2N) rows x group KiB should stay well inside an XCD's 4 MiB L2 beside the rows in flight
-            geo.group = (unsigned)(256 / SG_STREAM_TILE_SPL);      // 64 KiB of a tick row
+            geo.group = 64;                          // 64 KiB of a tick row
             if (geo.group > geo.strips) geo.group = geo.strips;
             const unsigned groups = (geo.strips + geo.group - 1) / geo.group;
             geo.total = (unsigned long long)groups * geo.group * geo.bands;
-            const unsigned long long blocks = (geo.total + SG_STREAM_TILE_WPB - 1) / SG_STREAM_TILE_WPB;
+            const unsigned long long blocks = (geo.total + STREAM_TILE_WPB - 1) / STREAM_TILE_WPB;
             if (blocks < 0x7fffff00ull) {
                 unsigned grid = ((unsigned)blocks + 7u) & ~7u;
                 job.aligned = 1;
-                hipLaunchKernelGGL((sg_bank_tile_kernel<N, FMA>), dim3(grid), dim3(64 * SG_STREAM_TILE_WPB), 0, st, job, taps, geo);
+                hipLaunchKernelGGL((sg_bank_tile_kernel<N, FMA>), dim3(grid), dim3(64 * STREAM_TILE_WPB), 0, st, job, taps, geo);
                 return 0;
             }
         }

@@ -14,17 +14,13 @@ namespace sg {
 template <int N>
 struct SRoll {
     static constexpr int WS = 2 * N + 1;
-    // rows loaded ahead of the arithmetic (A/B builds override).  Round 3, after the counters had said that a walk is short of
+    // rows loaded ahead of the arithmetic.  Round 3, after the counters had said that a walk is short of
     // requests in flight rather than of memory (profiles/r03_strip_walk_counters.txt): the sample-ring kernels (n <= 16) with 7 rows
     // ahead -- and, for the fused-multiply-add bank, at most TWO resident blocks per CU (8 waves; launch_bank_roll) -- run config 3's
     // block push in 0.389 ms instead of 0.404-0.417 (0.69 of the roofline; n = 4: 0.378 vs 0.407), the reference-order bank 0.451-0.460
     // instead of 0.467-0.469 at its full occupancy (it is bound by its two instructions per tap and needs the waves).  The
     // accumulator-ring kernels (n > 16) have their own ring of rows in flight (bank_accroll_item) and keep 4 blocks per CU.
-#ifdef SG_SROLL_P
-    static constexpr int P = SG_SROLL_P;
-#else
     static constexpr int P = N <= 16 ? 7 : 3;
-#endif
     static constexpr int U = WS + P;                         // ring slots = unroll factor of the tick loop
     static constexpr int NP = N + 1;                         // SGPR pairs holding taps 0..2N
 };
