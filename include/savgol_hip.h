@@ -273,12 +273,13 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter,
                              size_t images, Savgol2DBoundary boundary, int method, void *stream);
 
 /* Derivative frames (arithmetic of savgol2d_gradient / _hessian / _laplacian, src/savgol2d.c:462-618).  The Laplacian
- * uses the single summed kernel (scale_xx*Wxx + scale_yy*Wyy): no temporary frame, no add pass.  Outputs may be NULL
- * (skipped), like the reference.  Square windows use the separable kernels (fp32 rounding only vs the reference):
- * three Hessian frames, and frames whose rank the rolling-window kernel is not built for at that half window, come from
- * ONE read of each input tile (tile kernel); one or two frames otherwise are rolling-window launches (the gradient of
- * a half window <= 8: one launch for both frames; faster).  Other window shapes: one dense pass per
- * output.                                                                                                           */
+ * writes one frame, with no temporary frame and no add pass.  Outputs may be NULL (skipped), like the reference.
+ * Square windows use the separable kernels (fp32 rounding only vs the reference), one frame after the other: frames
+ * whose x derivative is the higher (gradient x, Hessian xx) run the horizontal pass first; the Hessian's xy and yy share
+ * one rolling-window launch where they have as many terms; the Laplacian is one frame of the summed kernel
+ * scale_xx*Wxx + scale_yy*Wyy.  Other window
+ * shapes: one pass per output as savgol2d_apply_batch_f32 method 0 runs it; the Laplacian computes both dense sums from
+ * one read of each input tile and adds them as the reference adds its two frames (bit-identical).  See DESIGN.md.    */
 int savgol2d_gradient_batch_f32(int half_win_x, int half_win_y, int poly_order,
                                 const float *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
                                 float *d_grad_x, float *d_grad_y, int out_stride, size_t out_image_pitch,

@@ -10,9 +10,9 @@
 // kernel that used to serve those is gone; sg2d_direct2_kernel below keeps its tile form for the rectangular Laplacian).
 // Kernels 2 and 3 (method 2 / auto): W is exactly low rank, W(x,y) = sum_t G_t(y) Q_t(x) with r <= 4 terms, so the
 // frame is filtered as r column passes and r row passes: 2 r (2n+1) FMAs per pixel instead of (2n+1)^2, back in
-// HBM-bound territory; fp32 rounding only (1e-7 level) against the reference.  sg_2d_roll.hip (half windows <= 8:
-// rolling column windows in registers, one launch per output frame) and sg_2d_sep.hip (any half window, up to three
-// output frames from one read of each LDS tile).
+// HBM-bound territory; fp32 rounding only (1e-7 level) against the reference.  enqueue_frame picks the kernel for one output
+// frame: sg_2d_hf.hip (x-dominant derivative frames, horizontal pass first), sg_2d_roll.hip (rolling column windows in
+// registers) or sg_2d_sep.hip (the tile kernel: square windows, any half window).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,6 +28,7 @@
 namespace sg {
 
 constexpr int T2_W = 64, T2_H = 16;                 // outputs per block: 64 wide, 16 tall (4 per thread)
+constexpr int SEP_FACTOR_FLOATS = SEP_MAX_TERMS * 2 * (2 * SAVGOL2D_MAX_HALF_WINDOW + 2);   // one frame's factors at the widest half window
 
 // Two dense windows over one read of the tile, each summed in the reference's order and scaled, then added: the reference's Laplacian
 // (savgol2d_laplacian, src/savgol2d.c:560-618: output = xx frame, temp = yy frame, output += temp) bit for bit, with no temporary frame
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void sg2d_add_kernel(float *__restrict__ out, 
 // separable factors per config, computed once (host least-squares solve + orthogonalisation)
 static int sep_factors_cached(const Savgol2DConfig *cfg, float *factors)
 {
-    struct Entry { Savgol2DConfig cfg; int terms; float f[SEP_MAX_TERMS * 2 * (2 * SAVGOL2D_MAX_HALF_WINDOW + 2)]; };
+    struct Entry { Savgol2DConfig cfg; int terms; float f[SEP_FACTOR_FLOATS]; };
     static std::mutex mu;
     static Entry cache[32];
     static int used = 0, next = 0;
@@ -114,7 +115,7 @@ static int sep_factors_cached(const Savgol2DConfig *cfg, float *factors)
 struct SummedKey { int n, order; float dx, dy; };
 static int summed_factors_cached(const SummedKey &key, const double *Wsum, float *factors)
 {
-    struct Entry { SummedKey key; int terms; float f[SEP_MAX_TERMS * 2 * (2 * SAVGOL2D_MAX_HALF_WINDOW + 2)]; };
+    struct Entry { SummedKey key; int terms; float f[SEP_FACTOR_FLOATS]; };
     static std::mutex mu;
     static Entry cache[16];
     static int used = 0, next = 0;
@@ -150,11 +151,17 @@ static const Savgol2DFilter *rect_filter_cached(const Savgol2DConfig *cfg, bool 
     return f;
 }
 
-// The rolling kernel on one output, in one launch where its taps fit the scalar registers (4 terms up to n = 8, 3 up to n = 12, 2
-// beyond), else in TWO: the first half of the terms, then the rest with job.accumulate (out += ...).  The second pass re-reads the
-// input and read-modify-writes the output -- 20 B per pixel instead of 8 -- which these arithmetic-bound shapes can afford: order 6
-// at n = 9 / 12 / 16: 1.83 / 2.25 / 3.15 ms per 16 frames on the tile kernel, two rolling passes 1.5-2 x faster (profiles/
-// r03_sweep_2d_orders.txt).  0 = launched, 1 = not covered.  `n` = the (larger) half window the factors are laid out for.
+// rect_filter_cached's answer for the length of one call: a filter the full cache did not keep is destroyed with the holder
+struct CachedFilter {
+    bool owned = false;
+    const Savgol2DFilter *f = nullptr;
+    const Savgol2DFilter *get(const Savgol2DConfig *cfg) { if (!f) f = rect_filter_cached(cfg, &owned); return f; }
+    CachedFilter() = default;
+    CachedFilter(const CachedFilter &) = delete;
+    CachedFilter &operator=(const CachedFilter &) = delete;
+    ~CachedFilter() { if (owned) savgol2d_destroy(const_cast<Savgol2DFilter *>(f)); }
+};
+
 // Do two frame batches share a byte?  EXACT for strided layouts (round 4 compared the bounding byte ranges only, which refused
 // side-by-side views of one buffer -- in = buf[:, :cols], out = buf[:, cols:], stride 2 cols -- and frames interleaved at a common pitch).
 // Units below are floats relative to `a`; a batch is the set { i*pitch + r*stride + c : i < images, r < rows, c < cols }.
@@ -210,9 +217,37 @@ static bool frames_overlap(const float *a, long long a_pitch, int a_stride, cons
     return false;
 }
 
-// Kernels whose x factor cancels harder than their y factor (sg2d_x_dominant: d^2/dx^2, the Hessian's xx frame, ...) run the HORIZONTAL pass first
-// (sg_2d_hf.hip): one launch per term, the later ones accumulating.  1 = not covered (no definite parity): the caller falls back to the
-// vertical-first kernels, nothing has been launched.
+// What every 2-D device entry point checks once its kernel is known to be valid, and the Job2D it starts from: job.in = d_in, the
+// caller sets out, scale and the tile counts.  0 = go on, 1 = nothing to do (no images), -1 = error.
+static int make_job(const char *who, int nx, int ny, const float *d_in, float *const *outs, int nout, int rows, int cols, int in_stride,
+                    long long in_pitch, int out_stride, long long out_pitch, size_t images, int boundary, Job2D &job)
+{
+    bool null = !d_in;
+    for (int i = 0; i < nout; ++i) null = null || !outs[i];
+    if (null) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (rows <= 0 || cols <= 0 || in_stride < cols || out_stride < cols) { sg_set_error("%s: bad image geometry", who); return -1; }
+    if (boundary == SAVGOL2D_BOUNDARY_VALID && (rows - 2 * ny <= 0 || cols - 2 * nx <= 0)) {
+        sg_set_error("%s: image smaller than the window", who);
+        return -1;
+    }
+    if (images == 0) return 1;
+    // No 2-D kernel may run in place: every output reads its neighbours' inputs, tiles of one frame run in any order, and the
+    // two-pass form of wide windows re-reads the input after the output has been written.  The reference's loop is no different
+    // (src/savgol2d.c:374-393 reads input rows it has long overwritten).  Refuse instead of returning garbage.
+    for (int i = 0; i < nout; ++i)
+        if (frames_overlap(d_in, in_pitch, in_stride, outs[i], out_pitch, out_stride, rows, cols, images)) {
+            sg_set_error("%s: input and output frames overlap (2-D filtering cannot run in place)", who);
+            return -1;
+        }
+    memset(&job, 0, sizeof(job));
+    job.in = d_in;
+    job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
+    job.in_pitch = in_pitch; job.out_pitch = out_pitch;
+    job.nx = nx; job.ny = ny;
+    job.boundary = (boundary == SAVGOL2D_BOUNDARY_VALID || boundary == SAVGOL2D_BOUNDARY_REFLECT) ? boundary : SAVGOL2D_BOUNDARY_CONSTANT;
+    return 0;
+}
+
 // What each term's x factor must SUM to (sg_2d_hf.hip, convert()): the horizontal-first kernel applies its taps to centred samples, s_k - c, and adds
 // c * sigma_t back -- with sigma_t taken from the REFERENCE's dense fp32 table instead of the rounded factor taps: least squares over the window rows y of
 //      scale * sum_x W[y][x]  ~=  sum_t sigma_t G_t(y)          (G_t = the fp32 column factors as the kernel mirrors them)
@@ -271,118 +306,139 @@ static bool hf_term_sums(int n, int terms, const float *factors, const Savgol2DF
     return true;
 }
 
-static int roll_passes_hf(int n, int terms, const Job2D &job, const float *factors, float scale, const Savgol2DFilter *dense, unsigned images, int cu_count, hipStream_t st)
+// One output frame of a separable kernel: `terms` terms laid out for the half window it is filtered with (a rectangular window's
+// factors zero-padded to its larger half window), output = scale * their sum.
+struct SepFrame {
+    const float *factors;
+    int terms;
+    float scale;
+    Savgol2DConfig cfg;                 // deriv_x / deriv_y set the pass order ((0, 0): the summed Laplacian); the dense table's configuration
+    const Savgol2DFilter *dense;        // that table if the caller holds it, else NULL: looked up when a pass needs it
+    float *out;
+};
+
+// Kernels whose x factor cancels harder than their y factor (sg2d_x_dominant: d/dx, d^2/dx^2, ...) run the HORIZONTAL pass first
+// (sg_2d_hf.hip): one launch per term, the later ones accumulating (the first two share one where the kernel has that form); the term
+// sums are fitted to `dense`, the frame's table (hf_term_sums).  0 = launched, 1 = not covered (no definite parity: nothing has been
+// launched), -1 = error.
+static int roll_passes_hf(int n, const Job2D &job, const SepFrame &fr, const Savgol2DFilter *dense, unsigned images, int cu_count, hipStream_t st)
 {
     const size_t tstride = (size_t)2 * (2 * n + 2);
-    for (int t = 0; t < terms; ++t) {
+    for (int t = 0; t < fr.terms; ++t) {
         float s;
-        if (!vector_parity(factors + t * tstride, n, &s) || !vector_parity(factors + t * tstride + (2 * n + 2), n, &s)) return 1;
+        if (!vector_parity(fr.factors + t * tstride, n, &s) || !vector_parity(fr.factors + t * tstride + (2 * n + 2), n, &s)) return 1;
     }
     float sigma[SEP_MAX_TERMS] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (dense && terms <= SEP_MAX_TERMS) hf_term_sums(n, terms, factors, dense, sigma);
+    hf_term_sums(n, fr.terms, fr.factors, dense, sigma);
     Job2D j = job;
     int t = 0;
-    if (terms >= 2 && terms <= SEP_MAX_TERMS && !job.accumulate &&
-        sg2d_launch_rolling_hf(n, j, factors, scale, sigma[0], factors + tstride, sigma[1], images, cu_count, st) == 0) {      // two terms from one trip of every row through LDS
-        t = 2;
-        j.accumulate = 1;
+    if (fr.terms >= 2) {                                     // two terms from one trip of every row through LDS
+        const int rc = sg2d_launch_rolling_hf(n, j, fr.factors, fr.scale, sigma[0], fr.factors + tstride, sigma[1], images, cu_count, st);
+        if (rc < 0) return rc;
+        if (rc == 0) { t = 2; j.accumulate = 1; }
     }
-    for (; t < terms; ++t) {
-        const int rc = sg2d_launch_rolling_hf(n, j, factors + t * tstride, scale, t < SEP_MAX_TERMS ? sigma[t] : 0.0f, nullptr, 0.0f, images, cu_count, st);
+    for (; t < fr.terms; ++t) {
+        const int rc = sg2d_launch_rolling_hf(n, j, fr.factors + t * tstride, fr.scale, sigma[t], nullptr, 0.0f, images, cu_count, st);
         if (rc != 0) return t == 0 ? rc : -1;
         j.accumulate = 1;
     }
     return 0;
 }
 
-static int roll_passes(int n, int terms, const Job2D &job, const float *factors, float scale, unsigned images, int cu_count, hipStream_t st,
-                       const Savgol2DFilter *hfirst_dense = nullptr)
+// The rolling kernel on one frame, in one launch where its taps fit the scalar registers (4 terms up to n = 8, 3 up to n = 12, 2
+// beyond), else in TWO: the first half of the terms, then the rest with job.accumulate (out += ...).  The second pass re-reads the
+// input and read-modify-writes the output -- 20 B per pixel instead of 8 -- which these arithmetic-bound shapes can afford: order 6
+// at n = 9 / 12 / 16: 1.83 / 2.25 / 3.15 ms per 16 frames on the tile kernel, two rolling passes 1.5-2 x faster (profiles/
+// r03_sweep_2d_orders.txt).  0 = launched, 1 = not covered, -1 = error.
+static int roll_passes(int n, const Job2D &job, const SepFrame &fr, unsigned images, int cu_count, hipStream_t st)
 {
-    if (hfirst_dense && !job.accumulate) {       // x-dominant kernel: horizontal pass first; the filter brings the dense table the term sums are fitted to
-        const int rc = roll_passes_hf(n, terms, job, factors, scale, hfirst_dense, images, cu_count, st);
-        if (rc != 1) return rc;
-    }
-    int rc = sg2d_launch_rolling(n, terms, job, factors, scale, images, cu_count, st);
-    if (rc != 1 || n < 9 || terms < 3 || terms > 4) return rc;      // split only what is "not covered" (1), never an error (-1)
+    int rc = sg2d_launch_rolling(n, fr.terms, job, fr.factors, fr.scale, images, cu_count, st);
+    if (rc != 1 || n < 9 || fr.terms < 3 || fr.terms > 4) return rc;      // split only what is "not covered" (1), never an error (-1)
     // 2 + 2 (or 2 + 1) rather than 3 + 1 where three terms fit: the accumulating pass moves 12 B per pixel and takes ~0.9 ms per 16
     // frames at n = 9 whether it carries one term or two, so it may as well carry two (3 + 1: 1.05 + 0.89 ms, 2 + 2: 0.75 + 0.93)
     const int first = 2;
     Job2D rest = job;
     rest.accumulate = 1;
     // try the second pass's instantiation first?  Both exist for every n >= 9 (NT <= 2), so the first failing means neither ran.
-    rc = sg2d_launch_rolling(n, first, job, factors, scale, images, cu_count, st);
+    rc = sg2d_launch_rolling(n, first, job, fr.factors, fr.scale, images, cu_count, st);
     if (rc != 0) return rc;
-    return sg2d_launch_rolling(n, terms - first, rest, factors + (size_t)first * 2 * (2 * n + 2), scale, images, cu_count, st);
+    return sg2d_launch_rolling(n, fr.terms - first, rest, fr.factors + (size_t)first * 2 * (2 * n + 2), fr.scale, images, cu_count, st);
+}
+
+// One output frame through the first kernel in this order that takes it: horizontal pass first (x-dominant frames), the rolling
+// kernel (in two passes where its terms do not fit one), the tile kernel (square windows, every half window).  Method 3 on a square
+// window goes straight to the tile kernel, whose first pass runs down the columns for y-dominant frames and on centred samples for x-
+// and y-dominant ones.  job: all but the output; n: the half window the factors are laid out for.  0 = launched, 1 = not covered
+// (nothing launched: a rectangular window beyond the rolling kernel's ranks), -1 = error.
+static int enqueue_frame(const char *who, DeviceCtx *ctx, const Job2D &job, int n, bool square, int method, const SepFrame &fr,
+                         size_t images, hipStream_t st)
+{
+    const bool xdom = sg2d_x_dominant(fr.cfg.deriv_x, fr.cfg.deriv_y), ydom = sg2d_y_dominant(fr.cfg.deriv_x, fr.cfg.deriv_y);
+    CachedFilter held;
+    const Savgol2DFilter *dense = fr.dense;
+    auto have_dense = [&] {                                  // on first use: most frames of a derivative call never need the table
+        if (!dense) dense = held.get(&fr.cfg);
+        if (!dense) sg_set_error("%s: weight computation failed", who);
+        return dense != nullptr;
+    };
+    const float *d_f = nullptr;
+    // chunks of images so that a launch indexes < 2^31 tiles
+    const size_t max_img = ((size_t)1 << 30) / ((size_t)((job.cols + 63) / 64) * (size_t)(job.rows + 1)) + 1;
+    for (size_t i0 = 0; i0 < images; i0 += max_img) {
+        const unsigned ni = (unsigned)(images - i0 < max_img ? images - i0 : max_img);
+        Job2D j = job;
+        j.in = job.in + (long long)i0 * job.in_pitch;
+        j.out = fr.out + (long long)i0 * job.out_pitch;
+        int rc = 1;
+        if (method != 3 || !square) {
+            if (xdom) rc = have_dense() ? roll_passes_hf(n, j, fr, dense, ni, ctx->cu_count, st) : -1;
+            if (rc == 1) rc = roll_passes(n, j, fr, ni, ctx->cu_count, st);
+        }
+        if (rc == 1 && square) {
+            if (!d_f) d_f = ctx_table(ctx, fr.factors, sizeof(float) * (size_t)fr.terms * 2 * (2 * n + 2), 0x5e000000u + (unsigned)n);
+            if (!d_f) return -1;
+            SepPlan plan;
+            memset(&plan, 0, sizeof(plan));
+            plan.outputs = 1; plan.terms[0] = fr.terms; plan.scale[0] = fr.scale; plan.out[0] = j.out;
+            plan.transposed = ydom ? 1 : 0;
+            if (xdom || ydom) {
+                if (!have_dense()) return -1;
+                plan.centre = hf_term_sums(n, fr.terms, fr.factors, dense, plan.first_sum, ydom, true) ? 1 : 0;
+            }
+            if (sg2d_launch_separable(n, j, plan, d_f, ni, ctx->cu_count, st) != 0) { sg_set_error("%s: no separable kernel for n=%d", who, n); return -1; }
+            rc = 0;
+        }
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 
 static int enqueue_2d(const char *who, const Savgol2DFilter *f, const float *d_in, int rows, int cols, int in_stride,
                       long long in_pitch, float *d_out, int out_stride, long long out_pitch, size_t images, int boundary,
                       int method, hipStream_t st)
 {
-    if (!f || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (!f) { sg_set_error("%s: NULL pointer", who); return -1; }
     const int nx = f->config.half_window_x, ny = f->config.half_window_y;
     if (nx < 1 || nx > SAVGOL2D_MAX_HALF_WINDOW || ny < 1 || ny > SAVGOL2D_MAX_HALF_WINDOW || !f->weights ||
         f->window_width != 2 * nx + 1 || f->window_height != 2 * ny + 1) {
         sg_set_error("%s: filter struct is not a valid Savgol2DFilter", who);
         return -1;
     }
-    if (rows <= 0 || cols <= 0 || in_stride < cols || out_stride < cols) { sg_set_error("%s: bad image geometry", who); return -1; }
-    if (boundary == SAVGOL2D_BOUNDARY_VALID && (rows - 2 * ny <= 0 || cols - 2 * nx <= 0)) {
-        sg_set_error("%s: image smaller than the window", who);
-        return -1;
-    }
-    if (images == 0) return 0;
-    {   // No 2-D kernel may run in place: every output reads its neighbours' inputs, tiles of one frame run in any order, and the
-        // two-pass form of wide windows re-reads the input after the output has been written.  The reference's loop is no different
-        // (src/savgol2d.c:374-393 reads input rows it has long overwritten).  Refuse instead of returning garbage.
-        if (frames_overlap(d_in, in_pitch, in_stride, d_out, out_pitch, out_stride, rows, cols, images)) {
-            sg_set_error("%s: input and output frames overlap (2-D filtering cannot run in place)", who);
-            return -1;
-        }
-    }
+    Job2D job;
+    int rc = make_job(who, nx, ny, d_in, &d_out, 1, rows, cols, in_stride, in_pitch, out_stride, out_pitch, images, boundary, job);
+    if (rc != 0) return rc > 0 ? 0 : -1;
     DeviceCtx *ctx = ctx_get();
     if (!ctx) return -1;
-    Job2D job;
-    memset(&job, 0, sizeof(job));
-    job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
-    job.in_pitch = in_pitch; job.out_pitch = out_pitch;
-    job.nx = nx; job.ny = ny;
-    job.boundary = (boundary == SAVGOL2D_BOUNDARY_VALID || boundary == SAVGOL2D_BOUNDARY_REFLECT) ? boundary : SAVGOL2D_BOUNDARY_CONSTANT;
     job.scale = f->scale;
     // method: 1 = dense window (bit-identical to the reference), 2 = separable passes (3 = its tile kernel only), 0 = separable when available
     if (method != 1) {
-        float factors[SEP_MAX_TERMS * 2 * (2 * SAVGOL2D_MAX_HALF_WINDOW + 2)];
+        float factors[SEP_FACTOR_FLOATS];
         const int terms = sep_factors_cached(&f->config, factors);
-        const bool square = nx == ny;
-        const int nmax = nx > ny ? nx : ny;                  // rectangular windows: factors zero-padded to the square window of half width nmax
         if (terms > 0) {
-            const float *d_f = nullptr;
-            // chunks of images so that a launch indexes < 2^31 tiles
-            const size_t tiles_per_image = (size_t)((cols + 63) / 64) * (size_t)(rows / 1 + 1);
-            const size_t max_img = tiles_per_image ? ((size_t)1 << 30) / tiles_per_image + 1 : images;
-            bool all_rolled = true;
-            for (size_t i0 = 0; i0 < images && all_rolled; i0 += max_img) {
-                const size_t ni = images - i0 < max_img ? images - i0 : max_img;
-                job.in = d_in + (long long)i0 * in_pitch;
-                job.out = d_out + (long long)i0 * out_pitch;
-                if (method != 3 || !square) {            // rolling-window kernel where it applies, else the tile kernel (square windows only)
-                    const int rc = roll_passes(nmax, terms, job, factors, f->scale, (unsigned)ni, ctx->cu_count, st,
-                                               sg2d_x_dominant(f->config.deriv_x, f->config.deriv_y) ? f : nullptr);
-                    if (rc == 0) continue;
-                }
-                if (!square) { all_rolled = false; break; }      // no rolling kernel of this rank at this half window: the dense kernel below
-                if (!d_f) d_f = ctx_table(ctx, factors, sizeof(float) * (size_t)terms * 2 * (2 * nx + 2), 0x5e000000u + (unsigned)nx);
-                if (!d_f) return -1;
-                SepPlan plan;
-                memset(&plan, 0, sizeof(plan));
-                plan.outputs = 1; plan.terms[0] = terms; plan.scale[0] = f->scale; plan.out[0] = job.out;
-                plan.transposed = sg2d_y_dominant(f->config.deriv_x, f->config.deriv_y) ? 1 : 0;
-                if (plan.transposed || sg2d_x_dominant(f->config.deriv_x, f->config.deriv_y)) {     // a derivative kernel's cancelling pass runs first, on centred samples
-                    plan.centre = hf_term_sums(nx, terms, factors, f, plan.first_sum, plan.transposed != 0, true) ? 1 : 0;
-                }
-                if (sg2d_launch_separable(nx, job, plan, d_f, (unsigned)ni, ctx->cu_count, st) != 0) { sg_set_error("%s: no separable kernel for n=%d", who, nx); return -1; }
-            }
-            if (all_rolled) return hip_ok(hipGetLastError(), who) ? 0 : -1;
+            const SepFrame fr = {factors, terms, f->scale, f->config, f, d_out};
+            rc = enqueue_frame(who, ctx, job, nx > ny ? nx : ny, nx == ny, method, fr, images, st);
+            if (rc == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
+            if (rc < 0) return -1;
         }
         if (method >= 2) { sg_set_error("%s: no separable kernel for this %dx%d window (rank > %d, or a rectangular window beyond the rolling kernel's ranks)", who, 2 * nx + 1, 2 * ny + 1, SEP_MAX_TERMS); return -1; }
     }
@@ -390,7 +446,7 @@ static int enqueue_2d(const char *who, const Savgol2DFilter *f, const float *d_i
         const size_t ni = images - i0 < 65535 ? images - i0 : 65535;
         job.in = d_in + (long long)i0 * in_pitch;
         job.out = d_out + (long long)i0 * out_pitch;
-        const int rc = sg2d_launch_dense_rolling(job, f->weights, ctx, (unsigned)ni, st);
+        rc = sg2d_launch_dense_rolling(job, f->weights, ctx, (unsigned)ni, st);
         if (rc != 0) {
             if (rc > 0) sg_set_error("%s: no dense kernel for a %dx%d window", who, 2 * nx + 1, 2 * ny + 1);
             return -1;
@@ -491,9 +547,10 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter, const float *d_in, in
                           out_stride, (long long)out_image_pitch, images, (int)boundary, method, static_cast<hipStream_t>(stream));
 }
 
-// ---- fused multi-output device entry points: ONE read of each input tile feeds every requested
-//      derivative frame; the Laplacian is a single filter with the summed kernel (no temporary frame, no add pass).
-//      Square windows run the separable kernel; other shapes fall back to one dense pass per output. ----
+// ---- device entry points of the derivative frames.  Square windows: a separable frame per output, each through enqueue_frame --
+//      x-dominant frames first, then the rest, two of them with the same number of terms (the Hessian's xy and yy) in ONE walk over
+//      the input; the Laplacian is one frame of the summed kernel (no temporary frame, no add pass).  Other window shapes: one pass per
+//      output through enqueue_2d; the Laplacian both dense sums over one read of each tile. ----
 namespace sg {
 
 struct DerivSpec { int dx, dy; float *out; };
@@ -502,97 +559,66 @@ static int enqueue_derivatives(const char *who, int nx, int ny, int order, const
                                size_t in_pitch, const DerivSpec *specs, int nspec, bool sum_into_one, int out_stride,
                                size_t out_pitch, size_t images, float delta_x, float delta_y, int boundary, hipStream_t st)
 {
-    if (!d_in || nspec <= 0) { sg_set_error("%s: NULL pointer", who); return -1; }
     Savgol2DConfig cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.half_window_x = (uint8_t)nx; cfg.half_window_y = (uint8_t)ny; cfg.poly_order = (uint8_t)order;
     cfg.delta_x = delta_x; cfg.delta_y = delta_y;
     if (nx < 0 || nx > 255 || ny < 0 || ny > 255 || order < 0 || order > 255) { sg_set_error("%s: invalid configuration", who); return -1; }
+    float *outs[SEP_MAX_OUTPUTS];
     for (int i = 0; i < nspec; ++i) {
         cfg.deriv_x = (uint8_t)specs[i].dx; cfg.deriv_y = (uint8_t)specs[i].dy;
         if (!sg2d_config_ok(&cfg)) { sg_set_error("%s: invalid configuration", who); return -1; }
+        outs[i] = specs[i].out;
     }
-    if (rows <= 0 || cols <= 0 || in_stride < cols || out_stride < cols) { sg_set_error("%s: bad image geometry", who); return -1; }
-    if (boundary == SAVGOL2D_BOUNDARY_VALID && (rows - 2 * ny <= 0 || cols - 2 * nx <= 0)) { sg_set_error("%s: image smaller than the window", who); return -1; }
-    if (images == 0) return 0;
-    for (int i = 0; i < nspec; ++i)
-        if (specs[i].out && frames_overlap(d_in, (long long)in_pitch, in_stride, specs[i].out, (long long)out_pitch, out_stride, rows, cols, images)) {
-            sg_set_error("%s: input and output frames overlap (2-D filtering cannot run in place)", who);
-            return -1;
-        }
+    Job2D job;
+    int rc = make_job(who, nx, ny, d_in, outs, nspec, rows, cols, in_stride, (long long)in_pitch, out_stride, (long long)out_pitch, images,
+                      boundary, job);
+    if (rc != 0) return rc > 0 ? 0 : -1;
     DeviceCtx *ctx = ctx_get();
     if (!ctx) return -1;
 
     if (nx != ny) {
-        // rectangular windows: the dense kernel, one launch per output frame; the Laplacian is ONE launch with the summed
-        // kernel sxx*Wxx + syy*Wyy (no temporary frame, no add pass, nothing but launches: capturable into a hipGraph)
-        const Savgol2DFilter *fs[SEP_MAX_OUTPUTS] = {nullptr, nullptr, nullptr};
-        bool owned[SEP_MAX_OUTPUTS] = {false, false, false};
-        int rc = 0;
-        for (int i = 0; i < nspec && rc == 0; ++i) {
+        CachedFilter fs[SEP_MAX_OUTPUTS];
+        for (int i = 0; i < nspec; ++i) {
             cfg.deriv_x = (uint8_t)specs[i].dx; cfg.deriv_y = (uint8_t)specs[i].dy;
-            fs[i] = rect_filter_cached(&cfg, &owned[i]);
-            if (!fs[i]) rc = -1;
+            if (!fs[i].get(&cfg)) return -1;
         }
-        if (rc == 0 && sum_into_one && nspec == 2) {
-            // the Laplacian of a rectangular window: BOTH dense sums from one read of the tile, added as the reference adds its two frames
-            // (bit-identical to savgol2d_laplacian; round 5 summed the two kernels into one table, whose re-rounded taps put the result
-            // 1.38e-6 from the oracle where the reference's xx + yy is at 1.22e-6)
-            const float *d_w1 = ctx_table(ctx, fs[0]->weights, sizeof(float) * (size_t)fs[0]->window_area, 0x2d000000u + (unsigned)(nx * 64 + ny));
-            const float *d_w2 = d_w1 ? ctx_table(ctx, fs[1]->weights, sizeof(float) * (size_t)fs[1]->window_area, 0x2d000000u + (unsigned)(nx * 64 + ny)) : nullptr;
-            if (!d_w1 || !d_w2) rc = -1;
-            else {
-                Job2D job;
-                memset(&job, 0, sizeof(job));
-                job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
-                job.in_pitch = (long long)in_pitch; job.out_pitch = (long long)out_pitch;
-                job.nx = nx; job.ny = ny;
-                job.boundary = (boundary == SAVGOL2D_BOUNDARY_VALID || boundary == SAVGOL2D_BOUNDARY_REFLECT) ? boundary : SAVGOL2D_BOUNDARY_CONSTANT;
-                job.scale = fs[0]->scale;
-                job.tiles_x = (cols + T2_W - 1) / T2_W;
-                job.tiles_y = (rows + T2_H - 1) / T2_H;
-                const size_t lds = sizeof(float) * (size_t)(2 * ((fs[0]->window_area + 3) & ~3) + (T2_W + 2 * nx) * (T2_H + 2 * ny));
-                for (size_t i0 = 0; i0 < images; i0 += 65535) {
-                    const size_t ni = images - i0 < 65535 ? images - i0 : 65535;
-                    job.in = d_in + (long long)i0 * (long long)in_pitch;
-                    job.out = specs[0].out + (long long)i0 * (long long)out_pitch;
-                    hipLaunchKernelGGL(sg2d_direct2_kernel, dim3((unsigned)(job.tiles_x * job.tiles_y), (unsigned)ni), dim3(256), lds, st, job, d_w1, d_w2, fs[1]->scale);
-                }
-                rc = hip_ok(hipGetLastError(), who) ? 0 : -1;
-            }
-        } else if (rc == 0 && sum_into_one) {
-            const int area = fs[0]->window_area;
-            std::vector<float> wsum((size_t)area);
-            for (int k = 0; k < area; ++k) {
-                double acc = 0.0;
-                for (int i = 0; i < nspec; ++i) acc += (double)fs[i]->scale * (double)fs[i]->weights[k];
-                wsum[(size_t)k] = (float)acc;
-            }
-            Savgol2DFilter summed = *fs[0];
-            summed.weights = wsum.data();
-            summed.scale = 1.0f;
-            rc = enqueue_2d(who, &summed, d_in, rows, cols, in_stride, (long long)in_pitch, specs[0].out, out_stride, (long long)out_pitch,
-                            images, boundary, 1, st);               // the table is copied into the device cache before this returns
-        } else if (rc == 0) {
-            for (int i = 0; i < nspec && rc == 0; ++i)
-                rc = enqueue_2d(who, fs[i], d_in, rows, cols, in_stride, (long long)in_pitch, specs[i].out, out_stride, (long long)out_pitch,
-                                images, boundary, 0, st);           // the rolling kernel on zero-padded factors where it is built for the rank, else dense
+        if (!sum_into_one) {
+            for (int i = 0; i < nspec; ++i)                  // the rolling kernel on zero-padded factors where it is built for the rank, else dense
+                if (enqueue_2d(who, fs[i].f, d_in, rows, cols, in_stride, (long long)in_pitch, specs[i].out, out_stride, (long long)out_pitch,
+                               images, boundary, 0, st) != 0) return -1;
+            return 0;
         }
-        for (int i = 0; i < nspec; ++i)
-            if (owned[i]) savgol2d_destroy(const_cast<Savgol2DFilter *>(fs[i]));
-        return rc;
+        // the Laplacian of a rectangular window: BOTH dense sums from one read of the tile, added as the reference adds its two frames
+        // (bit-identical to savgol2d_laplacian; round 5 summed the two kernels into one table, whose re-rounded taps put the result
+        // 1.38e-6 from the oracle where the reference's xx + yy is at 1.22e-6).  Nothing but launches: capturable into a hipGraph.
+        const Savgol2DFilter *fxx = fs[0].f, *fyy = fs[1].f;
+        const float *d_w1 = ctx_table(ctx, fxx->weights, sizeof(float) * (size_t)fxx->window_area, 0x2d000000u + (unsigned)(nx * 64 + ny));
+        const float *d_w2 = d_w1 ? ctx_table(ctx, fyy->weights, sizeof(float) * (size_t)fyy->window_area, 0x2d000000u + (unsigned)(nx * 64 + ny)) : nullptr;
+        if (!d_w1 || !d_w2) return -1;
+        job.scale = fxx->scale;
+        job.tiles_x = (cols + T2_W - 1) / T2_W;
+        job.tiles_y = (rows + T2_H - 1) / T2_H;
+        const size_t lds = sizeof(float) * (size_t)(2 * ((fxx->window_area + 3) & ~3) + (T2_W + 2 * nx) * (T2_H + 2 * ny));
+        for (size_t i0 = 0; i0 < images; i0 += 65535) {
+            const size_t ni = images - i0 < 65535 ? images - i0 : 65535;
+            job.in = d_in + (long long)i0 * (long long)in_pitch;
+            job.out = specs[0].out + (long long)i0 * (long long)out_pitch;
+            hipLaunchKernelGGL(sg2d_direct2_kernel, dim3((unsigned)(job.tiles_x * job.tiles_y), (unsigned)ni), dim3(256), lds, st, job, d_w1, d_w2, fyy->scale);
+        }
+        return hip_ok(hipGetLastError(), who) ? 0 : -1;
     }
 
-    const int n = nx, ws = 2 * n + 1;
-    static thread_local double Wd[33 * 33], Wsum[33 * 33];
-    float factors[SEP_MAX_OUTPUTS * SEP_MAX_TERMS * 2 * (2 * SAVGOL2D_MAX_HALF_WINDOW + 2)];
-    SepPlan plan;
-    memset(&plan, 0, sizeof(plan));
-    int total_terms = 0;
+    const int n = nx;
+    float factors[SEP_MAX_OUTPUTS][SEP_FACTOR_FLOATS];
+    SepFrame frames[SEP_MAX_OUTPUTS];
+    int nframes = 0;
     if (sum_into_one) {
-        // (the only summed form is the Laplacian: d = (2,0) + (0,2), which the key takes for granted)
+        // the Laplacian: ONE frame of the summed kernel sxx*Wxx + syy*Wyy (the only summed form: d = (2,0) + (0,2), which the key takes for granted)
+        static thread_local double Wd[33 * 33], Wsum[33 * 33];
+        const int ws = 2 * n + 1;
         const SummedKey key = {n, order, delta_x, delta_y};
-        int t = summed_factors_cached(key, nullptr, factors);
+        int t = summed_factors_cached(key, nullptr, factors[0]);
         if (t < 0) {
             for (int i = 0; i < ws * ws; ++i) Wsum[i] = 0.0;
             for (int i = 0; i < nspec; ++i) {
@@ -601,105 +627,37 @@ static int enqueue_derivatives(const char *who, int nx, int ny, int order, const
                 const double sc = (double)sg2d_scale(&cfg);
                 for (int k = 0; k < ws * ws; ++k) Wsum[k] += sc * Wd[k];
             }
-            t = summed_factors_cached(key, Wsum, factors);
+            t = summed_factors_cached(key, Wsum, factors[0]);
         }
         if (t <= 0) { sg_set_error("%s: kernel is not separable with <= %d terms", who, SEP_MAX_TERMS); return -1; }
-        plan.outputs = 1; plan.terms[0] = t; plan.scale[0] = 1.0f; plan.out[0] = specs[0].out;
-        total_terms = t;
+        cfg.deriv_x = 0; cfg.deriv_y = 0;
+        frames[nframes++] = SepFrame{factors[0], t, 1.0f, cfg, nullptr, specs[0].out};
     } else {
         for (int i = 0; i < nspec; ++i) {
             cfg.deriv_x = (uint8_t)specs[i].dx; cfg.deriv_y = (uint8_t)specs[i].dy;
-            float one[SEP_MAX_TERMS * 2 * (2 * SAVGOL2D_MAX_HALF_WINDOW + 2)];
-            const int t = sep_factors_cached(&cfg, one);
+            const int t = sep_factors_cached(&cfg, factors[i]);
             if (t <= 0) { sg_set_error("%s: kernel is not separable with <= %d terms", who, SEP_MAX_TERMS); return -1; }
-            memcpy(factors + (size_t)total_terms * 2 * (ws + 1), one, sizeof(float) * (size_t)t * 2 * (ws + 1));
-            plan.terms[plan.outputs] = t; plan.scale[plan.outputs] = sg2d_scale(&cfg); plan.out[plan.outputs] = specs[i].out;
-            plan.outputs++;
-            total_terms += t;
+            frames[nframes++] = SepFrame{factors[i], t, sg2d_scale(&cfg), cfg, nullptr, specs[i].out};
         }
     }
-    Job2D job;
-    memset(&job, 0, sizeof(job));
-    job.in = d_in;
-    job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
-    job.in_pitch = (long long)in_pitch; job.out_pitch = (long long)out_pitch;
-    job.nx = n; job.ny = n;
-    job.boundary = (boundary == SAVGOL2D_BOUNDARY_VALID || boundary == SAVGOL2D_BOUNDARY_REFLECT) ? boundary : SAVGOL2D_BOUNDARY_CONSTANT;
-    int odx[SEP_MAX_OUTPUTS] = {0, 0, 0}, ody[SEP_MAX_OUTPUTS] = {0, 0, 0};          // derivative orders of plan's outputs (the summed Laplacian: none)
-    if (!sum_into_one) {
-        // x-dominant frames (the Hessian's xx: deriv_x >= 2, deriv_x > deriv_y) run on their own with the HORIZONTAL pass first (sg_2d_hf.hip:
-        // the pass order that keeps them inside the parity rule); the other frames share their launches as before
-        float rest_factors[SEP_MAX_OUTPUTS * SEP_MAX_TERMS * 2 * (2 * SAVGOL2D_MAX_HALF_WINDOW + 2)];
-        SepPlan rest;
-        memset(&rest, 0, sizeof(rest));
-        int tb = 0, rest_terms = 0;
-        for (int o = 0; o < plan.outputs; ++o) {
-            const float *fo = factors + (size_t)tb * 2 * (ws + 1);
-            bool done = false;
-            if (sg2d_x_dominant(specs[o].dx, specs[o].dy)) {
-                job.out = plan.out[o];
-                cfg.deriv_x = (uint8_t)specs[o].dx; cfg.deriv_y = (uint8_t)specs[o].dy;
-                bool owned = false;
-                const Savgol2DFilter *dense = rect_filter_cached(&cfg, &owned);       // the reference's dense table of this frame (cached per configuration)
-                done = dense && roll_passes_hf(n, plan.terms[o], job, fo, plan.scale[o], dense, (unsigned)images, ctx->cu_count, st) == 0;
-                if (owned) savgol2d_destroy(const_cast<Savgol2DFilter *>(dense));
-            }
-            if (!done) {
-                odx[rest.outputs] = specs[o].dx; ody[rest.outputs] = specs[o].dy;
-                memcpy(rest_factors + (size_t)rest_terms * 2 * (ws + 1), fo, sizeof(float) * (size_t)plan.terms[o] * 2 * (ws + 1));
-                rest.terms[rest.outputs] = plan.terms[o]; rest.scale[rest.outputs] = plan.scale[o]; rest.out[rest.outputs] = plan.out[o];
-                rest.outputs++;
-                rest_terms += plan.terms[o];
-            }
-            tb += plan.terms[o];
-        }
-        if (rest.outputs == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
-        if (rest.outputs != plan.outputs) {
-            plan = rest;
-            total_terms = rest_terms;
-            memcpy(factors, rest_factors, sizeof(float) * (size_t)rest_terms * 2 * (ws + 1));
-        }
+    // x-dominant frames first, each on its own (horizontal pass first: the order that keeps them inside the parity rule); of the frames
+    // left, two with the same number of terms share one launch -- the input read once, the vertical ring shared (12 B per pixel of HBM
+    // traffic instead of 16)
+    int left[SEP_MAX_OUTPUTS], nleft = 0;
+    for (int i = 0; i < nframes; ++i) {
+        if (!sg2d_x_dominant(frames[i].cfg.deriv_x, frames[i].cfg.deriv_y)) left[nleft++] = i;
+        else if (enqueue_frame(who, ctx, job, n, true, 0, frames[i], images, st) != 0) return -1;
     }
-    // One or two outputs with a half window the rolling-window kernel covers: one launch of it per output is faster
-    // than the fused tile kernel even though the input is read once per output (measured, 4096^2 frames: gradient
-    // 4.4 ms vs 6.1 ms, Laplacian 2.2 ms vs 3.5 ms per 64 frames; three Hessian frames tie, so they stay fused).
-    // two outputs with the same number of terms (the gradient): ONE launch, the input is read once and both frames share the
-    // vertical ring (12 B per pixel of HBM traffic instead of 16)
-    if (plan.outputs == 2 && plan.terms[0] == plan.terms[1]) {
-        job.out = plan.out[0];
-        if (sg2d_launch_rolling2(n, plan.terms[0], job, factors, plan.scale[0], factors + (size_t)plan.terms[0] * 2 * (ws + 1), plan.scale[1],
-                                 plan.out[1], (unsigned)images, ctx->cu_count, st) == 0)
-            return hip_ok(hipGetLastError(), who) ? 0 : -1;
-    }
-    // everything else: one rolling launch (or pair of passes) per frame; the tile kernel, one frame at a time, for what the rolling kernels do not
-    // cover.  (Until round 5 three Hessian frames shared one walk / one LDS tile; since the xx frame runs horizontal-first on its own -- above --
-    // at most two frames are left, and the three-output instantiations are gone.)
-    int tbase = 0;
-    for (int o = 0; o < plan.outputs; ++o) {
-        const float *fo = factors + (size_t)tbase * 2 * (ws + 1);
-        job.out = plan.out[o];
-        const int rc = roll_passes(n, plan.terms[o], job, fo, plan.scale[o], (unsigned)images, ctx->cu_count, st);
+    if (nleft == 2 && frames[left[0]].terms == frames[left[1]].terms) {
+        const SepFrame &a = frames[left[0]], &b = frames[left[1]];
+        Job2D j = job;
+        j.out = a.out;
+        rc = sg2d_launch_rolling2(n, a.terms, j, a.factors, a.scale, b.factors, b.scale, b.out, (unsigned)images, ctx->cu_count, st);
         if (rc < 0) return -1;
-        if (rc != 0) {
-            SepPlan one;
-            memset(&one, 0, sizeof(one));
-            one.outputs = 1; one.terms[0] = plan.terms[o]; one.scale[0] = plan.scale[o]; one.out[0] = plan.out[o];
-            one.transposed = sg2d_y_dominant(odx[o], ody[o]) ? 1 : 0;       // the tile kernel's pass order (sg_2d_sep.hip)
-            if (!sum_into_one && (one.transposed || sg2d_x_dominant(odx[o], ody[o]))) {
-                cfg.deriv_x = (uint8_t)odx[o]; cfg.deriv_y = (uint8_t)ody[o];
-                bool owned = false;
-                const Savgol2DFilter *dense = rect_filter_cached(&cfg, &owned);
-                if (dense) {
-                    one.centre = hf_term_sums(n, plan.terms[o], fo, dense, one.first_sum, one.transposed != 0, true) ? 1 : 0;
-                    if (owned) savgol2d_destroy(const_cast<Savgol2DFilter *>(dense));
-                }
-            }
-            const float *d_f = ctx_table(ctx, fo, sizeof(float) * (size_t)plan.terms[o] * 2 * (ws + 1), 0x6d000000u + (unsigned)n);
-            if (!d_f) return -1;
-            if (sg2d_launch_separable(n, job, one, d_f, (unsigned)images, ctx->cu_count, st) != 0) { sg_set_error("%s: no separable kernel for n=%d", who, n); return -1; }
-        }
-        tbase += plan.terms[o];
+        if (rc == 0) nleft = 0;
     }
+    for (int i = 0; i < nleft; ++i)
+        if (enqueue_frame(who, ctx, job, n, true, 0, frames[left[i]], images, st) != 0) return -1;
     return hip_ok(hipGetLastError(), who) ? 0 : -1;
 }
 
@@ -761,27 +719,24 @@ static int host_derivatives(const char *who, int nx, int ny, int order, const Ho
                             int cols, int stride, float delta_x, float delta_y, int boundary, bool laplacian)
 {
     if (nspec == 0) return 0;
-    const Savgol2DFilter *fs[SEP_MAX_OUTPUTS] = {nullptr, nullptr, nullptr};
-    bool owned[SEP_MAX_OUTPUTS] = {false, false, false};
-    auto release = [&]() { for (int i = 0; i < nspec; ++i) if (owned[i] && fs[i]) savgol2d_destroy(const_cast<Savgol2DFilter *>(fs[i])); };
+    CachedFilter fs[SEP_MAX_OUTPUTS];
     for (int i = 0; i < nspec; ++i) {
         Savgol2DConfig cfg;
         memset(&cfg, 0, sizeof(cfg));
         cfg.half_window_x = (uint8_t)nx; cfg.half_window_y = (uint8_t)ny; cfg.poly_order = (uint8_t)order;
         cfg.deriv_x = (uint8_t)specs[i].dx; cfg.deriv_y = (uint8_t)specs[i].dy; cfg.delta_x = delta_x; cfg.delta_y = delta_y;
-        if (nx < 0 || nx > 255 || ny < 0 || ny > 255 || order < 0 || order > 255) { release(); fprintf(stderr, "savgol2d_create: invalid configuration\n"); return -1; }
-        fs[i] = rect_filter_cached(&cfg, &owned[i]);
-        if (!fs[i]) { release(); return -1; }
+        if (nx < 0 || nx > 255 || ny < 0 || ny > 255 || order < 0 || order > 255) { fprintf(stderr, "savgol2d_create: invalid configuration\n"); return -1; }
+        if (!fs[i].get(&cfg)) return -1;
     }
     const bool valid = boundary == SAVGOL2D_BOUNDARY_VALID;
-    if (!input || rows <= 0 || cols <= 0 || (valid && (rows - 2 * ny <= 0 || cols - 2 * nx <= 0))) { release(); return -1; }
+    if (!input || rows <= 0 || cols <= 0 || (valid && (rows - 2 * ny <= 0 || cols - 2 * nx <= 0))) return -1;
     DeviceCtx *ctx = ctx_get();
-    if (!ctx) { release(); fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
+    if (!ctx) { fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     const int dstride = (cols + 3) & ~3;
     const size_t frame = (size_t)rows * dstride;
     float *d_in = static_cast<float *>(ctx_arena(ctx, sizeof(float) * frame * (size_t)(1 + nspec)));
-    if (!d_in) { release(); fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
+    if (!d_in) { fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
     bool ok = hip_ok(hipMemcpy2D(d_in, sizeof(float) * dstride, input, sizeof(float) * stride, sizeof(float) * cols, rows, hipMemcpyHostToDevice),
                      "H2D copy");
     for (int i = 0; i < nspec && ok; ++i) {
@@ -793,7 +748,7 @@ static int host_derivatives(const char *who, int nx, int ny, int order, const Ho
                                                 hipMemcpyHostToDevice), "H2D copy");
             else ok = hip_ok(hipMemsetAsync(d_out, 0, sizeof(float) * frame, nullptr), "hipMemsetAsync");
         }
-        ok = ok && enqueue_2d(who, fs[i], d_in, rows, cols, dstride, 0, d_out, dstride, 0, 1, boundary, 1, nullptr) == 0;
+        ok = ok && enqueue_2d(who, fs[i].f, d_in, rows, cols, dstride, 0, d_out, dstride, 0, 1, boundary, 1, nullptr) == 0;
     }
     if (ok && laplacian) {
         float *d_a = d_in + frame, *d_b = d_in + 2 * frame;
@@ -809,7 +764,6 @@ static int host_derivatives(const char *who, int nx, int ny, int order, const Ho
                                     d_in + frame * (size_t)(1 + i) + (size_t)r0 * dstride + c0, sizeof(float) * dstride, sizeof(float) * nc, nr,
                                     hipMemcpyDeviceToHost), "D2H copy");
     }
-    release();
     if (!ok) { fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
     return 0;
 }

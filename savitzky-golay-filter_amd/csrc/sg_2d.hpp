@@ -79,7 +79,9 @@ inline bool vector_parity(const float *v, int n, float *sign)
 }
 
 constexpr int SEP_MAX_TERMS = 4;        // per output: rank of a bivariate polynomial of total degree <= 6 is at most 4 (parity in y)
-constexpr int SEP_MAX_OUTPUTS = 3;      // gradient = 2, Hessian = 3 outputs computed from ONE read of the input tile
+// The tile kernel runs one output frame per launch (sg2d_launch_separable refuses plan.outputs != 1); this still sizes SepPlan,
+// which the kernel takes by value, and the factor area of its LDS (sg_2d_sep.hip, launch_sep), so changing it changes the kernels.
+constexpr int SEP_MAX_OUTPUTS = 3;
 
 // what the separable kernel produces from each input tile: `outputs` frames, output o = scale[o] * sum of its terms
 struct SepPlan {
@@ -116,7 +118,8 @@ inline unsigned choose_bands(int rows, unsigned long long images_x_strips, unsig
 
 // sg_2d_roll.hip: rolling-window kernel, half windows 1..16.  The file is compiled once per
 // half-window group (SEP_ROLL_MIN_N..SEP_ROLL_MAX_N under the name SEP_ROLL_FN, see the Makefile) so the groups
-// build in parallel; each returns 0 = launched, 1 = not covered (other group, or the caller uses the tile kernel).
+// build in parallel; each returns 0 = launched, 1 = not covered (other group, or the caller uses the tile kernel), -1 = error.
+// The chains below ask the groups in turn and return the first answer that is not 1: the group that owns n decides.
 int sg2d_launch_rolling_g0(int n, int terms, const Job2D &job, const float *factors, float scale, unsigned images, int cu_count, hipStream_t st);
 int sg2d_launch_rolling_g1(int n, int terms, const Job2D &job, const float *factors, float scale, unsigned images, int cu_count, hipStream_t st);
 int sg2d_launch_rolling_g2(int n, int terms, const Job2D &job, const float *factors, float scale, unsigned images, int cu_count, hipStream_t st);
@@ -127,13 +130,14 @@ int sg2d_launch_rolling_g6(int n, int terms, const Job2D &job, const float *fact
 inline int sg2d_launch_rolling(int n, int terms, const Job2D &job, const float *factors, float scale, unsigned images, int cu_count,
                                hipStream_t st)
 {
-    if (sg2d_launch_rolling_g0(n, terms, job, factors, scale, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling_g1(n, terms, job, factors, scale, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling_g2(n, terms, job, factors, scale, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling_g3(n, terms, job, factors, scale, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling_g4(n, terms, job, factors, scale, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling_g5(n, terms, job, factors, scale, images, cu_count, st) == 0) return 0;
-    return sg2d_launch_rolling_g6(n, terms, job, factors, scale, images, cu_count, st);
+    static constexpr decltype(&sg2d_launch_rolling_g0) groups[] = {sg2d_launch_rolling_g0, sg2d_launch_rolling_g1, sg2d_launch_rolling_g2,
+                                                                    sg2d_launch_rolling_g3, sg2d_launch_rolling_g4, sg2d_launch_rolling_g5,
+                                                                    sg2d_launch_rolling_g6};
+    for (auto group : groups) {
+        const int rc = group(n, terms, job, factors, scale, images, cu_count, st);
+        if (rc != 1) return rc;
+    }
+    return 1;
 }
 
 // two output frames (job.out, out1) from one walk over the input; both outputs have `terms` (<= 3) terms
@@ -147,13 +151,14 @@ int sg2d_launch_rolling2_g6(int n, int terms, const Job2D &job, const float *f0,
 inline int sg2d_launch_rolling2(int n, int terms, const Job2D &job, const float *f0, float s0, const float *f1, float s1, float *out1,
                                 unsigned images, int cu_count, hipStream_t st)
 {
-    if (sg2d_launch_rolling2_g0(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling2_g1(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling2_g2(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling2_g3(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling2_g4(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling2_g5(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st) == 0) return 0;
-    return sg2d_launch_rolling2_g6(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st);
+    static constexpr decltype(&sg2d_launch_rolling2_g0) groups[] = {sg2d_launch_rolling2_g0, sg2d_launch_rolling2_g1, sg2d_launch_rolling2_g2,
+                                                                     sg2d_launch_rolling2_g3, sg2d_launch_rolling2_g4, sg2d_launch_rolling2_g5,
+                                                                     sg2d_launch_rolling2_g6};
+    for (auto group : groups) {
+        const int rc = group(n, terms, job, f0, s0, f1, s1, out1, images, cu_count, st);
+        if (rc != 1) return rc;
+    }
+    return 1;
 }
 
 // sg_2d_hf.hip: ONE term of a kernel with the HORIZONTAL pass first (kernels whose x factor cancels harder than their y factor: deriv_x >= 2,
@@ -165,9 +170,12 @@ int sg2d_launch_rolling_hf_g2(int n, const Job2D &job, const float *factors, flo
 inline int sg2d_launch_rolling_hf(int n, const Job2D &job, const float *factors, float scale, float sigma, const float *factors2, float sigma2, unsigned images, int cu_count,
                                   hipStream_t st)
 {
-    if (sg2d_launch_rolling_hf_g0(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st) == 0) return 0;
-    if (sg2d_launch_rolling_hf_g1(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st) == 0) return 0;
-    return sg2d_launch_rolling_hf_g2(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st);
+    static constexpr decltype(&sg2d_launch_rolling_hf_g0) groups[] = {sg2d_launch_rolling_hf_g0, sg2d_launch_rolling_hf_g1, sg2d_launch_rolling_hf_g2};
+    for (auto group : groups) {
+        const int rc = group(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st);
+        if (rc != 1) return rc;
+    }
+    return 1;
 }
 // which pass order suits a kernel in fp32 (sg_2d_hf.hip's header, tools/emulate_2d_passes.py, tools/gx_margin_probe.py): the pass that cancels harder -- the
 // derivative of higher order, FIRST derivatives included since the end of round 6 -- goes first

@@ -262,13 +262,12 @@ static int launch_dense(const Job2D &job, const float *d_w, unsigned images, int
 {
     typedef Dense<N> R;
     const unsigned strips = (unsigned)((job.cols + R::SW - 1) / R::SW);
-    static int per_cu = 0;                                   // resident blocks per CU of this instantiation
     const size_t lds = sizeof(float) * 4 * 2 * R::BUFW;
-    if (per_cu == 0) {
+    static const int per_cu = [&] {                          // resident blocks per CU of this instantiation
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sg2d_dense_roll_kernel<N, CAP>, 256, lds) != hipSuccess || nb < 1) nb = 2;
-        per_cu = nb > 4 ? 4 : nb;
-    }
+        return nb > 4 ? 4 : nb;
+    }();
     const unsigned nwaves = (unsigned)cu_count * (unsigned)per_cu * 4u;
     unsigned bands = choose_bands(job.rows, (unsigned long long)images * strips, nwaves, CAP > 0 ? job.ny : N, 1.0);   // warm-up rows are fed in full
     const int band_rows = (int)((job.rows + (int)bands - 1) / (int)bands);

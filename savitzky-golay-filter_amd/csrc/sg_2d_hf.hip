@@ -278,12 +278,11 @@ static int hf_launch(const Job2D &job, const HfTaps<N, NT> &taps, unsigned image
     if (job.out_stride % 4 == 0 && job.out_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.out) & 15u) == 0) aligned |= 2;
     const unsigned strips = (unsigned)((job.cols + R::SW - 1) / R::SW);
     const size_t lds = sizeof(float) * R::WPB * R::BUFW;
-    static int per_cu = 0;
-    if (per_cu == 0) {
+    static const int per_cu = [&] {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sg2d_rolling_hf_kernel<N, ACC, NT>, 64 * R::WPB, lds) != hipSuccess || nb < 1) nb = 1;
-        per_cu = nb > 4 ? 4 : nb;
-    }
+        return nb > 4 ? 4 : nb;
+    }();
     const unsigned nwaves = (unsigned)cu_count * (unsigned)per_cu * R::WPB;
     unsigned long long per_image;
     unsigned bands;

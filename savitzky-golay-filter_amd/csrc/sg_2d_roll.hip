@@ -734,15 +734,14 @@ static int launch_roll_kernel(const Job2D &job, const RollTaps<N, NT, NOUT> &tap
         if ((aligned & 7) != 7) return launch_roll_kernel<N, NT, NOUT, BOX, ACC, 0>(job, taps, out1, images, cu_count, st);
     }
     const unsigned strips = (unsigned)((job.cols + R::SW - 1) / R::SW);
-    static int per_cu = 0;                                   // resident blocks per CU of this instantiation
     constexpr unsigned WPB = (unsigned)roll_wpb(N, TR);
     size_t lds = sizeof(float) * WPB * 2 * NOUT * NT * R::BUFW;
-    if (per_cu == 0) {
+    static const int per_cu = [&] {                          // resident blocks per CU of this instantiation
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sg2d_rolling_kernel<N, NT, NOUT, BOX, ACC, TR>, 64 * WPB, lds) != hipSuccess || nb < 1)
             nb = WPB <= 8 ? 2 : 1;
-        per_cu = nb > (int)(16 / WPB) ? (int)(16 / WPB) : nb;
-    }
+        return nb > (int)(16 / WPB) ? (int)(16 / WPB) : nb;
+    }();
     const unsigned nwaves = (unsigned)cu_count * (unsigned)per_cu * WPB;
     // One item per wave, blocks handed out by the hardware dispatcher in order -- as in the 1-D kernel, and for the same reason: the
     // same items and bands on a persistent grid (resident waves striding over the items) were 1-5 % slower at every half window

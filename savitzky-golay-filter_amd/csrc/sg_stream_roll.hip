@@ -338,13 +338,13 @@ static int launch_bank_roll(const float *center, BankJob job, int cu_count, hipS
     for (int k = 0; k < R::WS; ++k) {
         if (k & 1) taps.w[k >> 1].y = center[k]; else taps.w[k >> 1].x = center[k];
     }
-    static int per_cu = 0;                                   // resident blocks per CU of this instantiation
-    if (per_cu == 0) {
+    static const int per_cu = [] {                           // resident blocks per CU of this instantiation
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sg_bank_roll_kernel<N, FMA>, 256, 0) != hipSuccess || nb < 1) nb = 2;
-        per_cu = nb > 4 ? 4 : nb;
-        if (FMA && N <= 16 && per_cu > 2) per_cu = 2;        // fewer waves, more rows in flight each (see SRoll::P)
-    }
+        if (nb > 4) nb = 4;
+        if (FMA && N <= 16 && nb > 2) nb = 2;                // fewer waves, more rows in flight each (see SRoll::P)
+        return nb;
+    }();
     // Where the tile form pays (profiles/r04_stream_tile.txt; config 3's shape, 65 536 streams x 4096 ... 16 384 ticks, five variants of
     // streams per lane x rows per tile x waves per block, strips per group 8 ... 256): the reference-order bank at n <= 12 (n = 4: 0.393 vs
     // 0.420 ms, n = 8: 0.408 vs 0.425); at n = 16 its 2n = 32 halo rows per 16-row tile (3 x the row reads out of L2) cancel the gain
