@@ -11,7 +11,7 @@
  * Each function names the reference routine whose arithmetic it performs.  All of them return
  * 0 on success and -1 on error unless stated otherwise; savgol_hip_last_error() has the text.
  * Launches are asynchronous on `stream`.  What "enqueue only" means, entry point by entry point:
- *   - savgol_apply[_valid]_batch_f32/f64, savgol2d_apply_batch_f32, savgol2d_gradient/hessian/laplacian_batch_f32 (square and
+ *   - savgol_apply[_valid]_batch_f32/f64, savgol_apply[_valid]_multi_batch_f32, savgol2d_apply_batch_f32, savgol2d_gradient/hessian/laplacian_batch_f32 (square and
  *     rectangular windows), savgol_streambank_push/_push_full/_push_block/_flush/_flush_leading/_reset: launches only --
  *     capturable into a hipGraph AFTER one warm-up call with the same filter: the FIRST call with a new filter content
  *     uploads its tables (hipMalloc + a synchronous hipMemcpy, then cached for the life of the process; tables are never
@@ -94,7 +94,8 @@ enum { SAVGOL_HIP_OPT_CORRECT_LEADING_EDGE = 1, SAVGOL_HIP_OPT_REFERENCE_SUMMATI
  *     set it before.  Default 0: the reference's behaviour.
  * SAVGOL_HIP_OPT_TILE_WIDTH: which of the two tile widths the 1-D batch kernels run with where both are built (fp32 half windows
  *   <= 18, fp64 <= 24).  0 (default): by job size -- the 12 / 16 KiB tile from 16384 tiles up, the 8 KiB tile below; 1: always the
- *   8 KiB tile; 2: always the wide one.  Same bits per output either way; a tuning and test knob.                                */
+ *   8 KiB tile; 2: always the wide one.  A tuning and test knob: smoothing filters give the same bits either way; derivative
+ *   filters run on tiles centred on their own mean, so their last bits depend on the tile width.                              */
 int         savgol_hip_set_option(int option, int value);
 /* The same switches PER CALL: the *_ex forms of the 1-D device entry points take them as flags, so two threads (or two
  * calls) can run different summation orders or tile widths at the same time; the options above are only the DEFAULTS the
@@ -191,6 +192,32 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter,
                                       const void *d_in, size_t in_stride, size_t in_offset, size_t in_channel_pitch,
                                       void *d_out, size_t out_stride, size_t out_offset, size_t out_channel_pitch,
                                       size_t channels, size_t count, unsigned flags, void *stream);
+/* Several filters on ONE batch in one pass: smoothing and derivatives (d = 0 / 1 / 2 ...) of the same signals read the input once.
+ * `filters` and `d_outs` are host arrays of `count` entries, 1 <= count <= SAVGOL_MULTI_MAX_FILTERS; d_outs[k] is a device pointer and every
+ * output has the pitch out_ld.  All filters share config.half_window and config.boundary (poly_order, derivative and time_step may differ;
+ * a mismatch returns -1 naming the field).  `flags` is a complete SAVGOL_BATCH_* word, as in the _ex calls.
+ * Output k is bit-identical to savgol_apply[_valid]_batch_f32_ex(filters[k], d_in, d_outs[k], ..., flags | SAVGOL_BATCH_PLAIN_SUMMATION, stream).
+ * Fused: 2 or 3 outputs per launch, 4 + 4 count bytes per input sample instead of count x 8; count = 4 is two launches of two (the input is
+ * read twice); count = 1 is the single call.  These routes stay count single calls (same contract, not fused):
+ *   - SAVGOL_BATCH_REFERENCE_SUMMATION;
+ *   - channels longer than 2^30 samples (the single calls' sub-row route);
+ *   - derivative filters where the single call takes the wide tile (half_window <= 18 with SAVGOL_BATCH_TILE_WIDE, or without a tile flag on
+ *     batches of 16384 wide tiles and more): a derivative filter's tiles are centred on their mean, so its bits depend on the tile width.
+ *     Pass SAVGOL_BATCH_TILE_NARROW to fuse them as well.  Smoothing filters fuse either way.
+ * Returns -1 before any device call on: a NULL filter / input / output pointer, count outside 1..4, mismatched half_window or boundary,
+ * length < window, pitches smaller than the row, and any d_outs[k] that shares a byte with d_in or another output (in place is not supported).
+ * Like the single calls it only enqueues (after one warm-up call with the same filters), so it can be captured into a graph.
+ * fp32 only: the fp64 kernel is issue-bound (65 fp64 FMAs per output), so three fused outputs triple its FMAs to save a third of its bytes. */
+#define SAVGOL_MULTI_MAX_FILTERS 4
+int savgol_apply_multi_batch_f32(const SavgolFilter *const *filters, int count,
+                                 const float *d_in, float *const *d_outs,
+                                 size_t channels, size_t length, size_t in_ld, size_t out_ld,
+                                 unsigned flags, void *stream);
+/* the same with savgol_apply_valid's outputs: length - 2n samples at d_outs[k][c*out_ld + 0..] */
+int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int count,
+                                       const float *d_in, float *const *d_outs,
+                                       size_t channels, size_t length, size_t in_ld, size_t out_ld,
+                                       unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------- stream bank --------- *
  * `streams` independent SavgolStream-equivalents advancing in lock step, state in HBM as a

@@ -32,6 +32,7 @@ SAVGOL_HIP_OPT_TILE_WIDTH = 5
 SAVGOL_STREAMBANK_FMA = 1
 SAVGOL_BATCH_REFERENCE_SUMMATION, SAVGOL_BATCH_PLAIN_SUMMATION, SAVGOL_BATCH_TILE_NARROW, SAVGOL_BATCH_TILE_WIDE = 1, 2, 4, 8
 SAVGOL_BATCH_CORRECT_LEADING_EDGE, SAVGOL_BATCH_BOUNDARY_AWARE, SAVGOL_BATCH_MOMENT_F64 = 16, 32, 64
+SAVGOL_MULTI_MAX_FILTERS = 4
 
 
 class SavgolConfig(C.Structure):
@@ -123,6 +124,8 @@ SIGNATURES = {
     "savgol_apply_valid_batch_f32_ex": (C.c_int, [_F, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_batch_f64_ex": (C.c_int, [_F, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_strided_batch_f32_ex": (C.c_int, [_F, _vp, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_valid_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_hip_default_flags": (C.c_uint, []),
     # savgol_hip.h: stream bank
     "savgol_streambank_create": (_vp, [C.POINTER(SavgolConfig), _sz]),
@@ -306,6 +309,33 @@ class Filter:
         y = torch.empty((ch, out_len), dtype=x.dtype, device=x.device)
         self.apply_batch(x, y, ch, length, length, out_len, dtype=dtype, valid=valid, stream=stream, flags=flags)
         return y
+
+
+def apply_multi_batch(filters, d_in, d_outs, channels, length, in_ld=None, out_ld=None, flags=0, valid=False, stream=None):
+    """savgol_apply[_valid]_multi_batch_f32: several Filters of one half window and boundary on one read of d_in (fp32 device memory).
+    d_outs[k] receives filters[k]'s output, bit-identical to filters[k].apply_batch(..., flags=flags | SAVGOL_BATCH_PLAIN_SUMMATION)."""
+    count = len(filters)
+    if len(d_outs) != count:
+        raise ValueError("one output per filter")
+    n = filters[0].n if count else 0
+    fs = (_F * max(count, 1))(*[f.ptr for f in filters])
+    outs = (_vp * max(count, 1))(*[_addr(o) for o in d_outs])
+    name = f"savgol_apply_{'valid_' if valid else ''}multi_batch_f32"
+    rc = getattr(lib(), name)(fs, count, _addr(d_in), outs, channels, length, length if in_ld is None else in_ld,
+                              (length - 2 * n if valid else length) if out_ld is None else out_ld, flags, _stream(stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} returned {rc}: {last_error()}")
+
+
+def apply_multi_tensor(filters, x, valid=False, flags=0, stream=None):
+    """x: contiguous 2-D float32 torch tensor [channels, length] on the GPU; returns one tensor per filter (same order)."""
+    import torch
+    assert x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32
+    ch, length = x.shape
+    out_len = length - 2 * filters[0].n if valid else length
+    ys = [torch.empty((ch, out_len), dtype=x.dtype, device=x.device) for _ in filters]
+    apply_multi_batch(filters, x, ys, ch, length, length, out_len, flags=flags, valid=valid, stream=stream)
+    return ys
 
 
 def synth(tensor, channel0=0, seed=0x5A17601A, stream=None):

@@ -189,6 +189,13 @@ bool filter_sane(const SavgolFilter *f, const char *who)
 // sub-rows by enqueue_long below -- the reference's savgol_apply takes a size_t length
 constexpr size_t LAUNCH_MAX_LENGTH = (size_t)1 << 30;
 
+// Job1D::xcd_chunk_log2 of the tile kernels (SAVGOL_HIP_1D_XCD_CHUNK_LOG2, default 6; see enqueue_batch)
+unsigned xcd_chunk_log2()
+{
+    static const unsigned xcd_chunk_env = [] { const char *e = getenv("SAVGOL_HIP_1D_XCD_CHUNK_LOG2"); return e ? (unsigned)atoi(e) : 6u; }();
+    return xcd_chunk_env;
+}
+
 template <typename T>
 int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out, size_t channels, size_t length,
                  size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags);
@@ -316,8 +323,7 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
     // front gigabytes away from the other seven).  Sampled over fresh placements of the two buffers inside one process, columns rotated
     // (tools/placement_1d.py, profiles/r05_placement_1d.txt): headline shape 5.53 against 5.65 ms median, ahead on every one of six buffer pairs; chunks
     // of 32 / 256 / 1024 blocks 5.64 / 5.60 / 5.60; launch order loses 15 %.  SAVGOL_HIP_1D_XCD_CHUNK_LOG2=0 is the old order.
-    static const unsigned xcd_chunk_env = [] { const char *e = getenv("SAVGOL_HIP_1D_XCD_CHUNK_LOG2"); return e ? (unsigned)atoi(e) : 6u; }();
-    job.xcd_chunk_log2 = xcd_chunk_env;
+    job.xcd_chunk_log2 = xcd_chunk_log2();
     job.in_ld = (long long)in_ld;
     job.out_ld = (long long)out_ld;
     job.length = (unsigned)length;
@@ -508,6 +514,149 @@ int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out
     }
     if (!sg::scratch_free(scratch, st, "scratch free (channel ends)")) ok = false;
     return ok ? 0 : -1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Several filters of one half window and one boundary mode on the same batch (savgol_apply[_valid]_multi_batch_f32): one read of the input for
+// 2 or 3 outputs (sg1d_multi_kernel, sg_k1d_multi.hpp).  Output k is the single call's with SAVGOL_BATCH_PLAIN_SUMMATION, bit for bit: the fused
+// kernel runs the plain kernel's staging, inner product and centring on the narrow tile.  What it cannot reproduce runs as single calls:
+//   * SAVGOL_BATCH_REFERENCE_SUMMATION and channels longer than LAUNCH_MAX_LENGTH (the single calls' own routes);
+//   * derivative outputs where the single call takes the WIDE tile (half windows <= 18 on big batches, or SAVGOL_BATCH_TILE_WIDE): a derivative
+//     filter's tile is centred on the mean of its body, so its bits depend on the tile width.  Smoothing outputs do not, and stay fused.
+// Four fused outputs are two launches of two (the input is read twice); one is the single call.
+// ------------------------------------------------------------------------------------------------
+int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count, const float *d_in, float *const *d_outs, size_t channels,
+                  size_t length, size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+{
+    if (!filters || !d_outs || !d_in) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (count < 1 || count > SAVGOL_MULTI_MAX_FILTERS) { sg_set_error("%s: count %d outside 1..%d", who, count, SAVGOL_MULTI_MAX_FILTERS); return -1; }
+    for (int k = 0; k < count; ++k) {
+        if (!filters[k] || !d_outs[k]) { sg_set_error("%s: NULL pointer (filters[%d] / d_outs[%d])", who, k, k); return -1; }
+        if (!filter_sane(filters[k], who)) return -1;
+    }
+    const SavgolFilter *f0 = filters[0];
+    const int n = f0->config.half_window, ws = f0->window_size;
+    for (int k = 1; k < count; ++k) {
+        if (filters[k]->config.half_window != n) {
+            sg_set_error("%s: filters[%d] has half_window %d, filters[0] %d (all filters need the same half_window)", who, k, (int)filters[k]->config.half_window, n);
+            return -1;
+        }
+        if (filters[k]->config.boundary != f0->config.boundary) {
+            sg_set_error("%s: filters[%d] has boundary %d, filters[0] %d (all filters need the same boundary)", who, k, (int)filters[k]->config.boundary,
+                         (int)f0->config.boundary);
+            return -1;
+        }
+    }
+    if (length < (size_t)ws) { sg_set_error("%s: data length (%zu) < window size (%d)", who, length, ws); return -1; }
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
+    if (in_ld < length || out_ld < out_len) { sg_set_error("%s: row pitch smaller than the row", who); return -1; }
+    if (channels == 0) return 0;
+    for (int k = 0; k < count; ++k) {
+        if (rows_overlap(d_in, in_ld, length, static_cast<const float *>(d_outs[k]), out_ld, out_len, channels)) {
+            sg_set_error("%s: d_outs[%d] overlaps d_in (the multi-output call does not run in place)", who, k);
+            return -1;
+        }
+        for (int j = 0; j < k; ++j)
+            if (rows_overlap(static_cast<const float *>(d_outs[j]), out_ld, out_len, static_cast<const float *>(d_outs[k]), out_ld, out_len, channels)) {
+                sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap", who, j, k);
+                return -1;
+            }
+    }
+
+    const unsigned single_flags = flags | SAVGOL_BATCH_PLAIN_SUMMATION;
+    auto single = [&](int k) { return enqueue_batch<float>(who, filters[k], d_in, d_outs[k], channels, length, in_ld, out_ld, variant, st, single_flags); };
+    if (count == 1 || (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) || length > LAUNCH_MAX_LENGTH) {
+        for (int k = 0; k < count; ++k)
+            if (single(k) != 0) return -1;
+        return 0;
+    }
+    // the tile the single calls take (enqueue_batch with plain summation: no moment kernels)
+    constexpr unsigned E = 4;
+    const int vpl = sg::VPL_NARROW, vpl_wide = sg::wide_vectors_per_lane(sizeof(float), n);
+    const int tile_mode = (flags & SAVGOL_BATCH_TILE_NARROW) ? 1 : ((flags & SAVGOL_BATCH_TILE_WIDE) ? 2 : 0);
+    const bool single_wide = vpl_wide != vpl && tile_mode != 1 &&
+                             (tile_mode == 2 || (unsigned long long)channels * ((length + 64u * vpl_wide * E - 1) / (64u * vpl_wide * E)) >= sg::WIDE_TILE_MIN_TILES);
+    int fused[SAVGOL_MULTI_MAX_FILTERS], nf = 0;
+    for (int k = 0; k < count; ++k) {
+        if (single_wide && filters[k]->config.derivative >= 1) { if (single(k) != 0) return -1; }
+        else fused[nf++] = k;
+    }
+    if (nf == 1) return single(fused[0]);
+    if (nf == 0) return 0;
+
+    DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    const int mode = (variant == FULL) ? (int)f0->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
+    const bool poly = mode == SAVGOL_BOUNDARY_POLYNOMIAL;
+    const bool want_edges = poly && variant == FULL;
+    const bool correct_edge = (flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) != 0;
+    const unsigned TW = 64u * (unsigned)vpl * E;
+
+    sg::JobMulti1D jm;
+    memset(&jm, 0, sizeof(jm));
+    sg::Job1D &job = jm.base;
+    job.xcd_chunk_log2 = xcd_chunk_log2();
+    job.in_ld = (long long)in_ld;
+    job.out_ld = (long long)out_ld;
+    job.length = (unsigned)length;
+    sg::set_tiles_per_channel(job, (unsigned)((length + TW - 1) / TW));
+    const bool interior_only = (variant == VALID) || poly;
+    job.store_lo = interior_only ? (unsigned)n : 0u;
+    job.store_hi = interior_only ? (unsigned)(length - n) : (unsigned)length;
+    job.out_shift = (variant == VALID) ? (unsigned)n : 0u;
+    job.flags = ((unsigned)mode & sg::JOB_MODE_MASK);
+    if (mode < 0 || mode > 255) job.flags = 255u;
+    if (((uintptr_t)d_in % 16 == 0) && (in_ld % E == 0)) job.flags |= sg::JOB_VEC_IN;
+    const unsigned tpc = job.tiles_per_channel;
+
+    // launches of 3, 2 or 2 + 2 outputs; within a launch the smoothing outputs first (they read the raw slab, sg_k1d_multi.hpp)
+    for (int g0 = 0; g0 < nf;) {
+        const int K = (nf - g0 == 4) ? 2 : (nf - g0);
+        int order[sg::MULTI_MAX_K], no = 0;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int i = g0; i < g0 + K; ++i)
+                if ((filters[fused[i]]->config.derivative >= 1) == (pass == 1)) order[no++] = fused[i];
+        sg::TapsMulti taps;
+        memset(&taps, 0, sizeof(taps));
+        jm.nraw = 0;
+        for (int j = 0; j < K; ++j) {
+            const SavgolFilter *f = filters[order[j]];
+            const FilterPlan *plan = plan_get(ctx, f, want_edges ? NEED_EDGES : 0u);
+            if (!plan) return -1;
+            taps.t[j] = plan->taps32;
+            jm.out[j] = d_outs[order[j]];
+            jm.edges[j] = want_edges ? plan->d_edges : nullptr;
+            jm.dt_inv[j] = dt_inverse(f);
+            unsigned fl = 0;
+            if (jm.dt_inv[j] != 1.0f) fl |= sg::JOB_SCALE;
+            if (((uintptr_t)d_outs[order[j]] % 16 == 0) && (out_ld % E == 0) && (job.out_shift % E == 0)) fl |= sg::JOB_VEC_OUT;
+            if (f->config.derivative >= 1) {
+                double wsum = 0.0;                                   // as enqueue_batch: what a constant comes out as, before dt_inv
+                for (int t = 0; t <= 2 * n; ++t) wsum += (double)f->center_weights[t];
+                jm.centre_sum[j] = (float)wsum;
+                fl |= sg::JOB_CENTRE;
+            } else {
+                ++jm.nraw;
+            }
+            if (want_edges && correct_edge && (f->config.derivative & 1)) fl |= sg::JOB_EDGE_NEGATE;
+            jm.flags[j] = fl;
+        }
+        // a launch stays below 2^24 blocks of four tiles, the edge items of every output counted
+        const size_t max_ch = (size_t)sg::MAX_TILES_PER_LAUNCH / ((size_t)tpc + 2 * (size_t)K);
+        for (size_t c0 = 0; c0 < channels; c0 += max_ch) {
+            const size_t nc = (channels - c0 < max_ch) ? channels - c0 : max_ch;
+            sg::JobMulti1D j = jm;
+            j.base.in = d_in + c0 * in_ld;
+            for (int o = 0; o < K; ++o) j.out[o] = static_cast<float *>(jm.out[o]) + c0 * out_ld;
+            j.base.total_tiles = (unsigned)(nc * tpc);
+            j.base.edge_items = want_edges ? (unsigned)(2 * nc * (size_t)K) : 0u;
+            unsigned blocks = (j.base.total_tiles + j.base.edge_items + 3u) / 4u;
+            blocks = (blocks + 7u) & ~7u;                                 // the XCD remap wants a multiple of 8
+            if (sg::launch_multi(n, K, j, taps, blocks, st) != 0) return -1;
+        }
+        g0 += K;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -742,6 +891,22 @@ int savgol_apply_valid_batch_f64_ex(const SavgolFilter *filter, const double *d_
 {
     if (!flags_ok("savgol_apply_valid_batch_f64_ex", flags)) return -1;
     return enqueue_batch<double>("savgol_apply_valid_batch_f64", filter, d_in, d_out, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_multi_batch_f32(const SavgolFilter *const *filters, int count, const float *d_in, float *const *d_outs, size_t channels, size_t length,
+                                 size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    const char *who = "savgol_apply_multi_batch_f32";
+    if (!flags_ok(who, flags)) return -1;
+    return enqueue_multi(who, filters, count, d_in, d_outs, channels, length, in_ld, out_ld, FULL, static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int count, const float *d_in, float *const *d_outs, size_t channels,
+                                       size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    const char *who = "savgol_apply_valid_multi_batch_f32";
+    if (!flags_ok(who, flags)) return -1;
+    return enqueue_multi(who, filters, count, d_in, d_outs, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_batch_f32(const SavgolFilter *filter, const float *d_in, float *d_out, size_t channels, size_t length,

@@ -92,6 +92,23 @@ struct JobStrided {
     unsigned    edge_items;             // as in Job1D
     const float *edges;
 };
+// The fused multi-output kernel, sg1d_multi_kernel<N, K> (sg_k1d_multi.hpp; savgol_apply_multi_batch_f32): K = 2 or 3 filters of one half window and
+// one boundary mode on one read of the input.  `base` carries the geometry, the input, the stored range and the boundary mode (its out, edges,
+// dt_inv, centre_sum and per-output flags are unused; no in-place fields); the arrays carry output k's own.  Outputs [0, nraw) are not centred
+// (derivative 0), outputs [nraw, K) are (JOB_CENTRE): the host orders them so.  Edge items: 2 K per channel (sg1d_multi_edge_item).
+constexpr int MULTI_MAX_K = 3;
+struct JobMulti1D {
+    Job1D       base;
+    void       *out[MULTI_MAX_K];
+    const float *edges[MULTI_MAX_K];    // output k's [n][2n+1] edge table (POLYNOMIAL, full variant), NULL = none
+    float       dt_inv[MULTI_MAX_K];
+    float       centre_sum[MULTI_MAX_K];
+    unsigned    flags[MULTI_MAX_K];     // JOB_SCALE, JOB_VEC_OUT, JOB_CENTRE, JOB_EDGE_NEGATE of output k
+    unsigned    nraw;
+};
+struct TapsMulti { Taps t[MULTI_MAX_K]; };
+static_assert(sizeof(JobMulti1D) + sizeof(TapsMulti) < 4096, "the multi-output kernarg stays under 4 KB");
+
 // Division by an invariant on the scalar unit (gfx950 has s_mul_hi_u32 but no scalar divide; left as `/` the compiler
 // runs the float-reciprocal sequence on the VECTOR unit, ~25 instructions per tile in a kernel that is VALU-issue bound).
 // For 0 <= t < 2^31 and 2^(l-1) < d <= 2^l:  floor(t / d) == (t * ceil(2^(31+l) / d)) >> (31 + l), and the multiplier
@@ -169,6 +186,15 @@ int sg1d_launch_strided_f32_g0(int n, const sg::JobStrided *job, const sg::Taps 
 int sg1d_launch_strided_f32_g1(int n, const sg::JobStrided *job, const sg::Taps *taps, unsigned grid, void *stream);
 int sg1d_launch_strided_f32_g2(int n, const sg::JobStrided *job, const sg::Taps *taps, unsigned grid, void *stream);
 int sg1d_launch_strided_f32_g3(int n, const sg::JobStrided *job, const sg::Taps *taps, unsigned grid, void *stream);
+// fused multi-output kernel, fp32, narrow tiles: one object per (output count, half-window group); 1 if this group owns n
+int sg1d_launch_multi2_g0(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
+int sg1d_launch_multi2_g1(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
+int sg1d_launch_multi2_g2(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
+int sg1d_launch_multi2_g3(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
+int sg1d_launch_multi3_g0(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
+int sg1d_launch_multi3_g1(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
+int sg1d_launch_multi3_g2(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
+int sg1d_launch_multi3_g3(int n, const sg::JobMulti1D *job, const sg::TapsMulti *taps, unsigned grid, void *stream);
 int sg1d_launch_f64_g0(int n, int wide, const sg::Job1D *job, const sg::Taps *taps, unsigned grid, void *stream);
 int sg1d_launch_f64_g1(int n, int wide, const sg::Job1D *job, const sg::Taps *taps, unsigned grid, void *stream);
 int sg1d_launch_f64_g2(int n, int wide, const sg::Job1D *job, const sg::Taps *taps, unsigned grid, void *stream);
@@ -234,6 +260,20 @@ inline int launch_strided(int n, const JobStrided &job, const Taps &taps, unsign
     if (!hit) { sg_set_error("no strided kernel for half_window %d", n); return -1; }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { sg_set_error("strided kernel launch failed: %s", hipGetErrorString(e)); return -1; }
+    return 0;
+}
+
+// k = 2 or 3 outputs
+inline int launch_multi(int n, int k, const JobMulti1D &job, const TapsMulti &taps, unsigned grid, hipStream_t st)
+{
+    const int hit = k == 2 ? (sg1d_launch_multi2_g0(n, &job, &taps, grid, st) || sg1d_launch_multi2_g1(n, &job, &taps, grid, st) ||
+                              sg1d_launch_multi2_g2(n, &job, &taps, grid, st) || sg1d_launch_multi2_g3(n, &job, &taps, grid, st))
+                 : k == 3 ? (sg1d_launch_multi3_g0(n, &job, &taps, grid, st) || sg1d_launch_multi3_g1(n, &job, &taps, grid, st) ||
+                              sg1d_launch_multi3_g2(n, &job, &taps, grid, st) || sg1d_launch_multi3_g3(n, &job, &taps, grid, st))
+                 : 0;
+    if (!hit) { sg_set_error("no multi-output kernel for half_window %d, %d outputs", n, k); return -1; }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { sg_set_error("multi-output kernel launch failed: %s", hipGetErrorString(e)); return -1; }
     return 0;
 }
 
