@@ -219,6 +219,32 @@ int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int c
                                        size_t channels, size_t length, size_t in_ld, size_t out_ld,
                                        unsigned flags, void *stream);
 
+/* 16-bit STORAGE for the 1-D batch call: fp16 or bf16 rows in device memory, fp32 arithmetic inside.  4 bytes per sample (16 -> 16 bit) or 6
+ * (16 bit -> fp32) instead of the fp32 call's 8; every kernel behind the batch call is bound by HBM bytes.
+ * d_in / d_out are device pointers to rows of `in_type` / `out_type` elements (SAVGOL_HIP_F16: IEEE binary16, SAVGOL_HIP_BF16: bfloat16);
+ * in_ld and out_ld count elements of their own buffer's type.  Type pairs (in -> out): f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32.
+ * Every other pair returns -1 naming the pair -- f32 -> f32 included: that is savgol_apply[_valid]_batch_f32[_ex].
+ * Arithmetic is exactly the fp32 call's: every input element is widened exactly to fp32 while its tile is staged, the tile runs the fp32 path
+ * unchanged (three-chain sum; block moments from half window 20 where the fp32 call takes them; centred tiles for derivative filters; dt
+ * scaling; POLYNOMIAL edge rows in the same launch) on the narrow tile, and a result is rounded to the output type ONCE, to nearest even, just
+ * before it is stored (NaN stays NaN; overflow to fp16 gives +-Inf as IEEE rounding does).
+ * CONTRACT: the output equals, bit for bit, savgol_apply[_valid]_batch_f32_ex(filter, widen(d_in), ..., flags | SAVGOL_BATCH_TILE_NARROW)
+ * rounded to nearest even into out_type; for out_type f32 it is that call's output itself.  NaN positions coincide; NaN payloads are free.
+ * `flags` is a complete SAVGOL_BATCH_* word, as in the _ex calls: SAVGOL_BATCH_PLAIN_SUMMATION, SAVGOL_BATCH_TILE_NARROW (implied) and
+ * SAVGOL_BATCH_CORRECT_LEADING_EDGE are served.  Returns -1 with a text, before any device call, on: SAVGOL_BATCH_REFERENCE_SUMMATION (the
+ * reference has no 16-bit form to be identical to), SAVGOL_BATCH_TILE_WIDE, flags of other calls (BOUNDARY_AWARE, MOMENT_F64) or unknown bits, an
+ * unserved type pair, a NULL pointer, length < window, a pitch smaller than the row, channels longer than 2^30 samples, and input and output rows
+ * that share a byte (in place included: a 16-bit row cannot hold its fp32 halo stash; use separate buffers).
+ * Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for 16-bit rows, 16 for fp32 output) move as vectors; any
+ * other base or pitch is served element by element.  Like the single calls it only enqueues (after one warm-up call with the same filter), so it
+ * can be captured into a graph.  Not served in 16 bit: the strided, multi-output, stream-bank and 2-D paths, int16 samples, fp32 -> 16-bit pairs. */
+enum { SAVGOL_HIP_F32 = 0, SAVGOL_HIP_F16 = 1, SAVGOL_HIP_BF16 = 2 };   /* storage type of a device buffer */
+int savgol_apply_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
+                           size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
+/* the same with savgol_apply_valid's outputs: length - 2n elements at d_out[c*out_ld + 0..] */
+int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
+                                 size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
+
 /* ---------------------------------------------------------------- stream bank --------- *
  * `streams` independent SavgolStream-equivalents advancing in lock step, state in HBM as a
  * structure of arrays (ring[slot][stream]).  Arithmetic of src/savgol_stream.c: single fp32

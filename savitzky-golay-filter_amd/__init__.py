@@ -33,6 +33,8 @@ SAVGOL_STREAMBANK_FMA = 1
 SAVGOL_BATCH_REFERENCE_SUMMATION, SAVGOL_BATCH_PLAIN_SUMMATION, SAVGOL_BATCH_TILE_NARROW, SAVGOL_BATCH_TILE_WIDE = 1, 2, 4, 8
 SAVGOL_BATCH_CORRECT_LEADING_EDGE, SAVGOL_BATCH_BOUNDARY_AWARE, SAVGOL_BATCH_MOMENT_F64 = 16, 32, 64
 SAVGOL_MULTI_MAX_FILTERS = 4
+SAVGOL_HIP_F32, SAVGOL_HIP_F16, SAVGOL_HIP_BF16 = 0, 1, 2          # storage type of a device buffer (savgol_apply[_valid]_batch_h16)
+_STORAGE = {"f32": SAVGOL_HIP_F32, "f16": SAVGOL_HIP_F16, "bf16": SAVGOL_HIP_BF16}
 
 
 class SavgolConfig(C.Structure):
@@ -126,6 +128,8 @@ SIGNATURES = {
     "savgol_apply_strided_batch_f32_ex": (C.c_int, [_F, _vp, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_valid_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_hip_default_flags": (C.c_uint, []),
     # savgol_hip.h: stream bank
     "savgol_streambank_create": (_vp, [C.POINTER(SavgolConfig), _sz]),
@@ -288,9 +292,22 @@ class Filter:
                                           dst.ctypes.data, out_stride, out_offset, count)
 
     # ---- device-pointer batch calls (torch tensors or raw addresses) ----
-    def apply_batch(self, d_in, d_out, channels, length, in_ld=None, out_ld=None, dtype="f32", valid=False, stream=None, flags=None, rel_tol=None):
+    def apply_batch(self, d_in, d_out, channels, length, in_ld=None, out_ld=None, dtype="f32", valid=False, stream=None, flags=None, rel_tol=None,
+                    out_dtype=None):
         """flags=None: the process-wide defaults (savgol_hip_set_option); an int: the *_ex entry point with exactly these SAVGOL_BATCH_* flags;
-        rel_tol (fp64 only): savgol_apply[_valid]_batch_f64_tol -- the accuracy the caller accepts picks the kernel."""
+        rel_tol (fp64 only): savgol_apply[_valid]_batch_f64_tol -- the accuracy the caller accepts picks the kernel.
+        dtype "f16" / "bf16": savgol_apply[_valid]_batch_h16 -- 16-bit rows in, out_dtype (None = the same type, or "f32") out, fp32 arithmetic;
+        flags is that call's complete SAVGOL_BATCH_* word (None = 0); in_ld / out_ld count elements of their own buffer."""
+        if dtype in ("f16", "bf16"):
+            assert rel_tol is None
+            name = f"savgol_apply_{'valid_' if valid else ''}batch_h16"
+            rc = getattr(lib(), name)(self.ptr, _addr(d_in), _STORAGE[dtype], _addr(d_out), _STORAGE[dtype if out_dtype is None else out_dtype], channels, length,
+                                      length if in_ld is None else in_ld, (length - 2 * self.n if valid else length) if out_ld is None else out_ld,
+                                      0 if flags is None else flags, _stream(stream))
+            if rc != 0:
+                raise RuntimeError(f"{name} returned {rc}: {last_error()}")
+            return
+        assert out_dtype is None or out_dtype == dtype, "out_dtype belongs to the 16-bit storage types"
         assert rel_tol is None or (dtype == "f64" and flags is None)
         name = f"savgol_apply_{'valid_' if valid else ''}batch_{dtype}" + ("_tol" if rel_tol is not None else ("" if flags is None else "_ex"))
         args = [self.ptr, _addr(d_in), _addr(d_out), channels, length, length if in_ld is None else in_ld,
@@ -299,15 +316,22 @@ class Filter:
         if rc != 0:
             raise RuntimeError(f"{name} returned {rc}: {last_error()}")
 
-    def apply_tensor(self, x, valid=False, stream=None, flags=None):
-        """x: contiguous 2-D torch tensor [channels, length] (float32 or float64) on the GPU."""
+    def apply_tensor(self, x, valid=False, stream=None, flags=None, out_dtype=None):
+        """x: contiguous 2-D torch tensor [channels, length] (float32, float64, float16 or bfloat16) on the GPU.
+        out_dtype (float16 / bfloat16 input only): None = the input's type, or torch.float32."""
         import torch
+        names = {torch.float32: "f32", torch.float64: "f64", torch.float16: "f16", torch.bfloat16: "bf16"}
+        if x.dtype not in names:
+            raise TypeError(f"apply_tensor serves float32, float64, float16 and bfloat16 tensors, not {x.dtype}")
+        dtype = names[x.dtype]
+        if out_dtype is not None and out_dtype != x.dtype and not (dtype in ("f16", "bf16") and out_dtype == torch.float32):
+            raise TypeError(f"apply_tensor: {x.dtype} -> {out_dtype} is not served")
         assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
-        dtype = {torch.float32: "f32", torch.float64: "f64"}[x.dtype]
         ch, length = x.shape
         out_len = length - 2 * self.n if valid else length
-        y = torch.empty((ch, out_len), dtype=x.dtype, device=x.device)
-        self.apply_batch(x, y, ch, length, length, out_len, dtype=dtype, valid=valid, stream=stream, flags=flags)
+        y = torch.empty((ch, out_len), dtype=x.dtype if out_dtype is None else out_dtype, device=x.device)
+        self.apply_batch(x, y, ch, length, length, out_len, dtype=dtype, valid=valid, stream=stream, flags=flags,
+                         out_dtype=None if out_dtype is None else names[out_dtype])
         return y
 
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sg_k1d_host.hpp"
+#include "sg_k1d_h16_host.hpp"
 #include "sg_runtime.hpp"
 
 using sg::DeviceCtx;
@@ -660,6 +661,126 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
 }
 
 // ------------------------------------------------------------------------------------------------
+// 16-bit storage (savgol_apply[_valid]_batch_h16): fp16 / bf16 rows in, the same type or fp32 out, on the kernels of sg_k1d_h16.hpp.  The job is the
+// one enqueue_batch<float> builds for the widened input under SAVGOL_BATCH_TILE_NARROW, field for field -- same kernel family (block moments where
+// the fp32 call takes them), same stored range, same centring, same edge items -- plus the two storage types; pitches and alignment are counted in
+// elements of their own buffer.  Every refusal comes before the first device call.
+// ------------------------------------------------------------------------------------------------
+const char *storage_name(int t)
+{
+    return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown";
+}
+
+// rows_overlap for buffers of different element sizes: everything in bytes
+bool rows_overlap_bytes(uintptr_t a0, size_t a_pitch, size_t a_len, uintptr_t b0, size_t b_pitch, size_t b_len, size_t channels)
+{
+    const uintptr_t a1 = a0 + (channels - 1) * a_pitch + a_len, b1 = b0 + (channels - 1) * b_pitch + b_len;
+    if (!(a0 < b1 && b0 < a1)) return false;                       // the whole extents are disjoint: the common case
+    if (a_pitch != b_pitch || channels == 1) return true;
+    const uintptr_t d = a0 <= b0 ? (b0 - a0) % a_pitch : (a_pitch - (a0 - b0) % a_pitch) % a_pitch;      // offset of a `b` row inside a's pitch
+    return d < a_len || d + b_len > a_pitch;
+}
+
+int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
+                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+{
+    if (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) {
+        sg_set_error("%s: SAVGOL_BATCH_REFERENCE_SUMMATION is not served on 16-bit storage (the reference has no 16-bit form to be identical to)", who);
+        return -1;
+    }
+    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on 16-bit storage (the call runs the narrow tile)", who); return -1; }
+    if (flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64)) {
+        sg_set_error("%s: flags 0x%x belong to other calls (BOUNDARY_AWARE: strided calls, MOMENT_F64: fp64 calls)", who, flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64));
+        return -1;
+    }
+    if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return -1; }
+    const bool in16 = in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16;
+    if (!in16 || !(out_type == in_type || out_type == SAVGOL_HIP_F32)) {
+        sg_set_error("%s: storage pair %s -> %s (%d -> %d) is not served (f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32; f32 -> f32 is savgol_apply_batch_f32)", who,
+                     storage_name(in_type), storage_name(out_type), in_type, out_type);
+        return -1;
+    }
+    if (!f || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (!filter_sane(f, who)) return -1;
+    const int n = f->config.half_window, ws = f->window_size;
+    if (length < (size_t)ws) { sg_set_error("%s: data length (%zu) < window size (%d)", who, length, ws); return -1; }
+    if (length > LAUNCH_MAX_LENGTH) { sg_set_error("%s: channels longer than 2^30 samples (%zu) are not served on 16-bit storage", who, length); return -1; }
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
+    if (in_ld < length || out_ld < out_len) { sg_set_error("%s: row pitch smaller than the row", who); return -1; }
+    if (channels == 0) return 0;
+    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
+    if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_out, out_ld * ob, out_len * ob, channels)) {
+        sg_set_error("%s: d_in and d_out overlap (the 16-bit-storage call does not run in place: input and output rows may not share a byte)", who);
+        return -1;
+    }
+
+    DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    const int mode = (variant == FULL) ? (int)f->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
+    const bool poly = (mode == SAVGOL_BOUNDARY_POLYNOMIAL);
+    const bool want_edges = poly && variant != VALID;
+    // the kernel family enqueue_batch<float> takes: block moments only where they cost no accuracy
+    const bool moment_safe = f->config.poly_order >= 2 && f->config.derivative <= 1;
+    const bool want_moment = n >= sg::MOMENTH_MIN_N && n <= sg::MOMENT_MAX_N && !(flags & SAVGOL_BATCH_PLAIN_SUMMATION) && moment_safe;
+    const FilterPlan *plan = plan_get(ctx, f, (want_edges ? NEED_EDGES : 0u) | (want_moment ? NEED_MOMENT : 0u));
+    if (!plan) return -1;
+    const float *d_moment = (want_moment && plan->moment_terms > 0) ? plan->d_moment : nullptr;
+
+    constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
+    const unsigned TW = 64u * (unsigned)sg::VPL_NARROW * E;
+    sg::JobH16 jh;
+    memset(&jh, 0, sizeof(jh));
+    jh.in_type = (unsigned)in_type;
+    jh.out_type = (unsigned)out_type;
+    sg::Job1D &job = jh.base;
+    job.xcd_chunk_log2 = xcd_chunk_log2();
+    job.in_ld = (long long)in_ld;
+    job.out_ld = (long long)out_ld;
+    job.length = (unsigned)length;
+    sg::set_tiles_per_channel(job, (unsigned)((length + TW - 1) / TW));
+    job.dt_inv = dt_inverse(f);
+    const bool interior_only = (variant == VALID) || poly;
+    job.store_lo = interior_only ? (unsigned)n : 0u;
+    job.store_hi = interior_only ? (unsigned)(length - n) : (unsigned)length;
+    job.out_shift = (variant == VALID) ? (unsigned)n : 0u;
+    job.flags = ((unsigned)mode & sg::JOB_MODE_MASK);
+    if (mode < 0 || mode > 255) job.flags = 255u;
+    if (job.dt_inv != 1.0f) job.flags |= sg::JOB_SCALE;
+    if (((uintptr_t)d_in % (E * ib) == 0) && (in_ld % E == 0)) job.flags |= sg::JOB_VEC_IN;
+    if (((uintptr_t)d_out % (E * ob) == 0) && (out_ld % E == 0) && (job.out_shift % E == 0)) job.flags |= sg::JOB_VEC_OUT;
+    if (f->config.derivative >= 1) {
+        double wsum = 0.0;                                               // as enqueue_batch: what a constant comes out as, before dt_inv
+        for (int k = 0; k <= 2 * n; ++k) wsum += (double)f->center_weights[k];
+        job.centre_sum = (float)wsum;
+        job.flags |= sg::JOB_CENTRE;
+    }
+    if (want_edges) {
+        job.edges = plan->d_edges;
+        if ((flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) && (f->config.derivative & 1)) job.flags |= sg::JOB_EDGE_NEGATE;
+    }
+    const unsigned tpc = job.tiles_per_channel;
+    const size_t max_ch = (size_t)sg::MAX_TILES_PER_LAUNCH / ((size_t)tpc + 2);      // a launch stays below 2^24 blocks of four tiles
+    for (size_t c0 = 0; c0 < channels; c0 += max_ch) {
+        const size_t nc = (channels - c0 < max_ch) ? channels - c0 : max_ch;
+        job.in = static_cast<const char *>(d_in) + c0 * in_ld * ib;
+        job.out = static_cast<char *>(d_out) + c0 * out_ld * ob;
+        job.total_tiles = (unsigned)(nc * tpc);
+        job.edge_items = want_edges ? (unsigned)(2 * nc) : 0u;
+        unsigned blocks = (job.total_tiles + job.edge_items + 3u) / 4u;
+        blocks = (blocks + 7u) & ~7u;                                    // the XCD remap wants a multiple of 8
+        int rc;
+        if (d_moment)
+            rc = plan->moment_terms == 3 ? sg1d_launch_h16_momenth_t3(n, &jh, d_moment, blocks, st)
+               : plan->moment_terms == 5 ? sg1d_launch_h16_momenth_t5(n, &jh, d_moment, blocks, st)
+                                         : sg1d_launch_h16_momenth_t7(n, &jh, d_moment, blocks, st);
+        else
+            rc = sg::launch_h16(n, jh, plan->taps32, blocks, st);
+        if (rc != 0) return -1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Long host-pointer signals: upload, filter and download in chunks so that the two directions of the host link run at the
 // same time (round 1 ran H2D -> kernel -> D2H back to back: 6.9 Gsamples/s at 2^26 samples, half of a full-duplex link).
 //   main thread : for every chunk  H2D(samples up to the chunk's right halo) -> reference-order kernel on [a_k, b_k) -> event
@@ -907,6 +1028,18 @@ int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int c
     const char *who = "savgol_apply_valid_multi_batch_f32";
     if (!flags_ok(who, flags)) return -1;
     return enqueue_multi(who, filters, count, d_in, d_outs, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
+                           size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_h16("savgol_apply_batch_h16", filter, d_in, in_type, d_out, out_type, channels, length, in_ld, out_ld, FULL, static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
+                                 size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_h16("savgol_apply_valid_batch_h16", filter, d_in, in_type, d_out, out_type, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_batch_f32(const SavgolFilter *filter, const float *d_in, float *d_out, size_t channels, size_t length,
