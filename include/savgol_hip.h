@@ -104,8 +104,10 @@ int         savgol_hip_set_option(int option, int value);
 enum { SAVGOL_BATCH_REFERENCE_SUMMATION = 1u, SAVGOL_BATCH_PLAIN_SUMMATION = 2u, SAVGOL_BATCH_TILE_NARROW = 4u, SAVGOL_BATCH_TILE_WIDE = 8u,
        SAVGOL_BATCH_CORRECT_LEADING_EDGE = 16u, SAVGOL_BATCH_BOUNDARY_AWARE = 32u /* strided calls only */,
        SAVGOL_BATCH_MOMENT_F64 = 64u /* fp64 calls, half_window 24..32: block moments replace the taps on the lanes' common block (~36 multiply-adds
-                                        per output instead of 65).  The block's share comes from the polynomial fitted to the fp32 table, so the
-                                        result is within ~1e-7 (bar: 1e-6) of the default fp64 path instead of its 1e-12.  Opt-in for that reason. */ };
+                                        per output instead of 65).  The block's share is a least-squares projection of the block's own promoted taps,
+                                        so the result is within ~1e-7 (bar: 1e-6) of the default fp64 path instead of its 1e-12 -- on zero-mean data
+                                        and equally on data riding on an offset, a ramp or a parabola (the projection keeps the taps' moments of
+                                        order < 3 exactly; tested to offsets of 1e3 and slopes of 0.5 per sample).  Opt-in for that reason. */ };
 unsigned    savgol_hip_default_flags(void);
 /* Diagnostic (host only, no device needed): the constant table the half-lane block-moment kernel (fp32 batch calls, half windows 20..32:
  * csrc/sg_k1d_momenth.hpp; layout in csrc/sg_k1d_host.hpp, at most SAVGOL_HIP_MOMENT_TABLE_FLOATS floats).  Returns the number of block
@@ -113,6 +115,12 @@ unsigned    savgol_hip_default_flags(void);
  * are not a polynomial), -1 on NULL.                                                                                                       */
 #define SAVGOL_HIP_MOMENT_TABLE_FLOATS 400
 int         savgol_hip_momenth_table(const SavgolFilter *filter, float *table);
+/* The same for the fp64 block-moment kernel (savgol_apply[_valid]_batch_f64_tol / SAVGOL_BATCH_MOMENT_F64, half windows 24..32:
+ * csrc/sg_k1d_moment64.hpp; layout MOMENT64_OFF_W / _PHI / _C in csrc/sg_k1d_host.hpp, SAVGOL_HIP_MOMENT64_TABLE_DOUBLES doubles).  Same return
+ * convention: 3, 5 or 7 block moments, 0 when the filter keeps the tap-by-tap kernel (half windows outside 24..32, poly_order > 6, tables that
+ * are not a polynomial), -1 on NULL.                                                                                                        */
+#define SAVGOL_HIP_MOMENT64_TABLE_DOUBLES 278
+int         savgol_hip_moment64_table(const SavgolFilter *filter, double *table);
 /* Diagnostic (host only): the fit behind the fused stream bank's block-moment tiles (csrc/sg_stream_dma.hip, half windows 12..20).  `center_weights`:
  * the 2n+1 fp32 taps a bank applies; `coefficients`: 3 x SAVGOL_HIP_STREAM_MOMENT_OFFSETS floats, [s][off] = weight of moment s (basis 1, t - 3.5,
  * (t - 3.5)^2 - 5.25 on t = 0..7) of the 8-tick block that starts `off` taps into a window.  Returns the number of moments (1..3), 0 when the
@@ -162,7 +170,11 @@ int savgol_apply_batch_f64_ex(const SavgolFilter *filter, const double *d_in, do
  * the caller accepts, and it picks the kernel.  rel_tol >= 1e-6 -- the bar BASELINE's fp64 configs state -- runs the block-moment kernel at half
  * windows 24..32 when the filter's table is the polynomial savgol_create builds (measured <= 1.5e-7 of the oracle, 0.78-0.84 of the HBM roofline at
  * n = 32 against the default's 0.66-0.70); a tighter rel_tol, other half windows and hand-edited tables run the tap-by-tap kernel (1e-12).  Same
- * process-wide defaults as the plain entry points otherwise.  The _ex flag SAVGOL_BATCH_MOMENT_F64 is the same choice as a flag.           */
+ * process-wide defaults as the plain entry points otherwise.  The _ex flag SAVGOL_BATCH_MOMENT_F64 is the same choice as a flag.
+ * What the 1.5e-7 holds for: poly_order <= 6, derivatives 0..2, every boundary mode and VALID, on the synthetic workload (zero-mean tones plus
+ * noise) AND on signals of unit variation riding on an offset up to 1e3, a ramp up to 0.5 per sample or a parabola (tests/test_gpu_1d.py,
+ * test_f64_tolerance_call_on_offsets_and_ramps): the kernel's replacement taps keep the table's moments of order 0, 1, 2 to rounding, so what
+ * lies under the signal meets no error beyond double rounding at its own size.  savgol_hip_moment64_table returns the table for inspection.  */
 int savgol_apply_batch_f64_tol(const SavgolFilter *filter, const double *d_in, double *d_out,
                                size_t channels, size_t length, size_t in_ld, size_t out_ld,
                                double rel_tol, void *stream);

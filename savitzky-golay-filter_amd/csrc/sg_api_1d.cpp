@@ -919,6 +919,13 @@ int savgol_hip_momenth_table(const SavgolFilter *filter, float *table)
     return sg1d_momenth_prepare(filter->config.half_window, filter->center_weights, table);
 }
 
+int savgol_hip_moment64_table(const SavgolFilter *filter, double *table)
+{
+    static_assert(SAVGOL_HIP_MOMENT64_TABLE_DOUBLES == sg::MOMENT64_TABLE_DOUBLES, "the header states the table's size");
+    if (!filter || !table) { sg_set_error("savgol_hip_moment64_table: NULL pointer"); return -1; }
+    return sg1d_moment64_prepare(filter->config.half_window, filter->center_weights, table);
+}
+
 // Medium host signals: two hipMemcpy calls cost more than the filter.  Between these lengths the CPU copies the signal into
 // pinned, device-visible host memory, the kernel reads it and writes its result across the link itself, and one stream
 // synchronise ends the call: launch + synchronise instead of H2D + launch + D2H.  Same kernel, same bits.  Measured

@@ -19,9 +19,12 @@
 //   * M1 multiply-adds per output for the block's share.
 // 240 + 25 (M1 + 2) + 16 M1 = 495 instructions at n = 32, M1 = 5, instead of 1040.  All constants come through scalar loads.
 //
-// Accuracy.  The block's share uses the POLYNOMIAL fitted to the fp32 table in double (sg1d_moment64_prepare), not the table's own
-// fp32-rounded entries: the result differs from the promoted-table oracle by the fit's residual (<= 3e-7 of the largest tap, the rounding
-// already in the reference's table; measured ~1e-7 normwise) -- inside north_star's 1e-6, outside the default path's 1e-12.  Hence opt-in.
+// Accuracy.  The block's share uses, per output, the least-squares PROJECTION of the block's own promoted taps onto the block's M1 Legendre terms
+// (sg1d_moment64_prepare), not the table's fp32-rounded entries themselves: the result differs from the promoted-table oracle by the projection's
+// residual (the fp32 rounding already in the reference's table, <= 3e-7 of the largest tap per tap; measured ~1e-7 normwise on zero-mean data) --
+// inside north_star's 1e-6, outside the default path's 1e-12.  Hence opt-in.  The residual is orthogonal to every polynomial of degree < M1 on the
+// block, so an offset, a ramp or a parabola under the signal meets no error at all; the same ~1e-7 holds on such inputs (tested to offsets of 1e3
+// and 0.5 per sample; tests/test_moment_table.py checks the tables' moments of order 0..2 on the host, tests/test_gpu_1d.py the kernel).
 #pragma once
 
 #include "sg_k1d.hpp"

@@ -143,7 +143,11 @@ extern "C" int sg1d_momenth_prepare(int n, const float *w, float *table)
 }
 
 // The fp64 kernel (sg_k1d_moment64.hpp; savgol_apply_batch_f64_tol / SAVGOL_BATCH_MOMENT_F64): 16 outputs per lane, the block X[LO .. HI) = 2n - 14 samples.  Everything
-// stays in double: the taps applied one by one are exact promotions of the fp32 table, the block's share comes from the fitted polynomial.
+// stays in double: the taps applied one by one are exact promotions of the fp32 table, and the block's share is the least-squares projection of
+// the block's OWN promoted taps onto the block's basis.  The fit of the whole window only decides whether the path is taken and with how many
+// terms.  (Projecting the fitted polynomial instead left the table's fp32 rounding in the replaced taps as differences that do not sum to zero:
+// 2e-9 ... 1e-8 of sum|w|, which an offset of 1e3 under a derivative filter turned into 1e-4 of the output.  A least-squares residual is
+// orthogonal to the basis, hence to every polynomial of degree < terms on the block: constants, ramps and parabolas under the signal meet none.)
 extern "C" int sg1d_moment64_prepare(int n, const float *w, double *table)
 {
     if (n < sg::MOMENT_MIN_N || n > sg::MOMENT_MAX_N) return 0;
@@ -151,7 +155,6 @@ extern "C" int sg1d_moment64_prepare(int n, const float *w, double *table)
     const CentreFit cf = fit_centre_taps(n, w);
     if (!cf.terms) return 0;
     const int terms = cf.terms;
-    auto p = [&](double k) { return cf.at(k); };
     memset(table, 0, sizeof(double) * sg::MOMENT64_TABLE_DOUBLES);
     for (int k = 0; k < 15; ++k) table[sg::MOMENT64_OFF_W + k] = (double)w[k];
     double phi[2 * sg::MOMENT64_MAX_PAIRS][MAXT];
@@ -165,7 +168,7 @@ extern "C" int sg1d_moment64_prepare(int n, const float *w, double *table)
             double Pr[MAXT];
             const int tm = t < BLOCK / 2 ? t : BLOCK - 1 - t;
             for (int s = 0; s < terms; ++s) Pr[s] = (t < BLOCK / 2 || !(s & 1)) ? phi[tm][s] : -phi[tm][s];
-            const double q = p((double)(LO + t - r - OFF));
+            const double q = (double)w[LO + t - r - OFF];             // tap 15 + t - r: 0 .. 2n over r = 0..15, t = 0..BLOCK-1
             for (int s = 0; s < terms; ++s) { b[s] += Pr[s] * q; for (int u = 0; u < terms; ++u) G[s][u] += Pr[s] * Pr[u]; }
         }
         if (!solve(terms, G, b, c)) return 0;

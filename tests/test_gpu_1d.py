@@ -1255,3 +1255,140 @@ def test_derivative_filters_on_signals_with_a_large_offset(sg, sgo, torch_gpu, n
             hi = o.apply_f64(x)[:, n:L - n]
             ref = o.apply(x)[:, n:L - n]
             check(normwise(got, hi), fp32_bar(normwise(ref, hi)), ("derivative filter, offset", n, m, d, off))
+
+
+# ------------------------------------------------------------------------------------------------
+# the fp64 tolerance call on signals that are not zero-mean
+# ------------------------------------------------------------------------------------------------
+TREND_FILTERS = [(4, 0), (4, 1), (4, 2), (2, 1), (2, 2), (3, 1), (6, 2), (5, 1)]
+TRENDS = [(off, slope, 0.0) for off in (0.0, 10.0, 1e3) for slope in (0.0, 0.05, 0.5)] + [(1e3, 0.5, 1e-3)]       # (offset, slope per sample, curvature)
+TRENDS_SHORT = [(1e3, 0.0, 0.0), (1e3, 0.5, 0.0), (1e3, 0.5, 1e-3)]
+
+
+def trended(rng, channels, length, off, slope, curv):
+    """sin(0.01 t) a_c + N(0, 0.1) riding on off + slope t + curv t^2, built on the host in double"""
+    t = np.arange(length, dtype=np.float64)
+    base = np.sin(0.01 * t)[None, :] * np.linspace(0.5, 1.5, channels)[:, None] + rng.normal(0, 0.1, (channels, length))
+    return base + (off + slope * t + curv * t * t)[None, :]
+
+
+def oracle_rounding(x, w_rows, dt, d, ref):
+    """how far the double oracle itself may sit from the exact answer on these samples, normwise: |x| 2^-53 sum|w| / dt^d against max|ref|.
+    A case whose value approaches the bar under test cannot be refereed by this oracle."""
+    return float(np.max(np.abs(x)) * 2.0 ** -53 * np.abs(w_rows).sum(axis=1).max() / (np.float32(dt) ** d) / np.max(np.abs(ref)))
+
+
+@pytest.mark.parametrize("n", [32, 31, 30, 29, 28, 27, 26, 25, 24])
+def test_f64_tolerance_call_on_offsets_and_ramps(sg, sgo, torch_gpu, n):
+    """savgol_apply[_valid]_batch_f64_tol(rel_tol = 1e-6) -- the block-moment kernel of csrc/sg_k1d_moment64.hpp -- on inputs that are NOT zero-mean:
+    offsets 0 / 10 / 1e3, ramps of 0.05 and 0.5 per sample, one parabola, under sin(0.01 t) a_c + N(0, 0.1).  Every test of that kernel used sg.synth
+    data (two zero-mean sines plus noise), where a block share that does not keep the table's tap sums measures 1e-7; on an offset of 1e3 a
+    second-derivative filter then stood at 1e-4 of the oracle with rel_tol = 1e-6 stated.  Expected values: the fp64 oracle (promoted fp32 tables,
+    double accumulation), never another kernel.  Bars:
+      * tolerance call, full and VALID: 1e-6, the number the API states, through check() so the margin log has every comparison;
+      * the oracle's own rounding on each input (oracle_rounding) must stay below 1e-8, or the comparison would say nothing;
+      * the default call on the same input: the forward bound of a (2n+1)-term dot product that
+        test_randomized_configurations_within_the_dot_product_error_bound uses, (2n+2) 2^-53 max_row sum|w| max|x| / dt^d -- two correct double
+        sums in different orders differ by rounding at the offset's size, so the flat 1e-12 is kept for the offset-free input only.
+    All four boundary modes, time steps 1 and 0.25, lengths with interior tiles, a channel-end tile and a single short row.
+    Reference loop: savgol_apply's centre loop, src/savgolFilter.c:763-766, on fp64 data (oracle: SURVEY 8c)."""
+    torch = torch_gpu
+    rng = np.random.default_rng(7100 + n)
+    ch = 3
+    worst = {}
+    # the parabola on three interior tiles and the short rows only: at 70001 samples it reaches 4.9e6, past what the oracle can referee at 1e-8
+    for length, trends in ((70001, TRENDS[:-1]), (3 * 4096 + 2 * n + 5, TRENDS[-1:]), (2 * n + 1, TRENDS_SHORT), (1024 + 2 * n + 3, TRENDS_SHORT)):
+        for (off, slope, curv) in trends:
+            xh = trended(rng, ch, length, off, slope, curv)
+            x = torch.from_numpy(xh).cuda()
+            for fi, (m, d) in enumerate(TREND_FILTERS):
+                for mode in range(4):
+                    dt = 1.0 if (fi + mode) % 2 == 0 else 0.25
+                    f, o = sg.Filter(n, m, d, dt, mode), sgo.Filter(n, m, d, dt, mode)
+                    ref = o.apply_f64(xh)
+                    rows = np.vstack([f.center_weights[None, :], f.edge_weights]).astype(np.float64)
+                    label = (n, m, d, mode, dt, length, off, slope, curv)
+                    assert oracle_rounding(xh, rows, dt, d, ref) < 1e-8, label
+                    y0, y6 = torch.empty_like(x), torch.empty_like(x)
+                    f.apply_batch(x, y0, ch, length, dtype="f64")
+                    f.apply_batch(x, y6, ch, length, dtype="f64", rel_tol=1e-6)
+                    torch.cuda.synchronize()
+                    e6 = normwise(y6.cpu().numpy(), ref)
+                    check(e6, 1e-6, ("f64 tolerance call, trend",) + label)
+                    key = (d, "offset-free" if off == 0 and slope == 0 else "offset" if slope == 0 else "parabola" if curv else "ramp")
+                    worst[key] = max(worst.get(key, 0.0), e6)
+                    bound = (2 * n + 2) * 2.0 ** -53 * np.abs(rows).sum(axis=1).max() * np.abs(xh).max() / (np.float32(dt) ** d)
+                    err0 = np.abs(y0.cpu().numpy() - ref).max()
+                    assert err0 <= bound, ("default fp64 call, trend",) + label + (err0, bound)
+                    if off == 0 and slope == 0:
+                        assert normwise(y0.cpu().numpy(), ref) < TOL_F64, label
+                    if length > 2 * n + 1:
+                        v6 = torch.empty((ch, length - 2 * n), dtype=torch.float64, device="cuda")
+                        f.apply_batch(x, v6, ch, length, dtype="f64", valid=True, rel_tol=1e-6)
+                        torch.cuda.synchronize()
+                        check(normwise(v6.cpu().numpy(), ref[:, n:-n]), 1e-6, ("f64 tolerance call, trend, VALID",) + label)
+                    if length > 4 * n and mode == fi % 4:
+                        # still the block-moment kernel, not a quiet return to the taps (the fit refuses one of these filters: n = 31, m = 6, d = 2)
+                        assert torch.equal(y6, y0) == ((n, m, d) == (31, 6, 2)), label
+                        yf = torch.empty_like(x)
+                        f.apply_batch(x, yf, ch, length, dtype="f64", flags=sg.SAVGOL_BATCH_MOMENT_F64)
+                        torch.cuda.synchronize()
+                        assert torch.equal(yf, y6), label                     # the _ex flag is the same choice: same bits
+    print(f"n={n}: f64 tolerance call, worst normwise distance from the fp64 oracle per (derivative, input class): " +
+          ", ".join(f"d={k[0]} {k[1]}: {v:.2e}" for k, v in sorted(worst.items())))
+
+
+def test_f64_tolerance_call_in_place_and_captured_on_an_offset(sg, sgo, torch_gpu):
+    """the tolerance call in place (d_out == d_in) and replayed from a captured graph, on an offset of 1e3 under a second-derivative filter: both
+    bit-identical to the out-of-place call, which is inside 1e-6 of the fp64 oracle"""
+    torch = torch_gpu
+    rng = np.random.default_rng(7200)
+    ch, length = 4, 50003
+    for n in (32, 27):
+        xh = trended(rng, ch, length, 1e3, 0.0, 0.0)
+        x = torch.from_numpy(xh).cuda()
+        for mode in (0, 2):
+            f = sg.Filter(n, 4, 2, 1.0, mode)
+            ref = sgo.Filter(n, 4, 2, 1.0, mode).apply_f64(xh)
+            want = torch.empty_like(x)
+            f.apply_batch(x, want, ch, length, dtype="f64", rel_tol=1e-6)          # (also the warm-up call a capture needs: tables uploaded)
+            torch.cuda.synchronize()
+            check(normwise(want.cpu().numpy(), ref), 1e-6, ("f64 tolerance call, offset 1e3, out of place", n, mode))
+            buf = x.clone()
+            f.apply_batch(buf, buf, ch, length, dtype="f64", rel_tol=1e-6)
+            torch.cuda.synchronize()
+            assert torch.equal(buf, want), (n, mode, "in place")
+            out = torch.full_like(x, float("nan"))
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s):
+                    f.apply_batch(x, out, ch, length, dtype="f64", rel_tol=1e-6, stream=s)
+            out.fill_(float("nan"))
+            g.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(out, want), (n, mode, "graph replay")
+
+
+@pytest.mark.parametrize("n,m", [(5, 3), (8, 3), (16, 2), (21, 4), (25, 4), (32, 4)])
+def test_derivative_filters_on_signals_with_a_ramp(sg, sgo, torch_gpu, n, m):
+    """test_derivative_filters_on_signals_with_a_large_offset knows offsets only, and a tile's mean does not remove a ramp: the centred tiles of the
+    default fp32 kernels see slope x (tile width / 2) at a tile's ends.  Slopes of 0.05 and 0.5 per sample at offsets 0 and 1e3, d = 1 and 2, the
+    interior of every boundary mode; the same rule -- max(1e-6, 1.1 x the reference's own fp32 error on the same samples) against the double oracle.
+    Reference loop: src/savgolFilter.c:763-766."""
+    torch = torch_gpu
+    rng = np.random.default_rng(90 + n)
+    L = 20000
+    t = np.arange(L, dtype=np.float64)
+    base = np.sin(0.01 * t)[None, :] * np.linspace(0.5, 1.5, 3)[:, None] + rng.normal(0, 0.1, (3, L))
+    for d in (1, 2):
+        for off in (0.0, 1000.0):
+            for slope in (0.05, 0.5):
+                x = (base + off + slope * t[None, :]).astype(np.float32)
+                for mode in range(4):
+                    f, o = sg.Filter(n, m, d, 0.5, mode), sgo.Filter(n, m, d, 0.5, mode)
+                    got = f.apply_tensor(torch.from_numpy(x).cuda()).cpu().numpy()[:, n:L - n]
+                    hi = o.apply_f64(x)[:, n:L - n]
+                    ref = o.apply(x)[:, n:L - n]
+                    check(normwise(got, hi), fp32_bar(normwise(ref, hi)), ("derivative filter, ramp", n, m, d, off, slope, mode))

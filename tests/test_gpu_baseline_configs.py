@@ -9,7 +9,7 @@ Size-independent properties (linearity, constant/ramp preservation) cover what t
 import numpy as np
 import pytest
 
-from tests._util import normwise
+from tests._util import check, normwise
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +100,14 @@ def test_config5_fp64_second_derivative_long_channels(sg, sgo, torch_gpu):
     z = f.apply_tensor(2.5 * x + 1e-3 * t)
     d = (z - (2.5 * y + 1e-3 * ft)).abs().max().item()
     assert d < 1e-10 * max(1.0, z.abs().max().item()), d
+    # the tolerance call at the bar the config states, on the same channels riding on 1e3 + 1e-3 t (added on the device): sensor data sit on offsets
+    # and drifts, the synthetic workload does not, and a block-moment share that loses the table's tap sums shows only there
+    torch.add(x, t, alpha=1e-3, out=z)
+    z.add_(1e3)
+    f.apply_batch(z, ft, ch, length, dtype="f64", rel_tol=1e-6)
+    torch.cuda.synchronize()
+    ref = sgo.Filter(32, 4, 2, 1.0, 0).apply_f64(z[sample].cpu().numpy())
+    check(normwise(ft[sample].cpu().numpy(), ref), 1e-6, ("config 5, tolerance call, 1e3 + 1e-3 t under the signal", ch, length))
 
 
 def _need_hbm(torch, nbytes):
@@ -195,6 +203,13 @@ def test_config5_full_slice_in_chunks(sg, sgo, torch_gpu):
             f.apply_batch(x, z, chunk, length, dtype="f64", rel_tol=1e-9)
             torch.cuda.synchronize()
             assert torch.equal(z, y)
+            # one more pass: the chunk riding on 1e3 + 1e-3 t (added on the device), the tolerance call at the config's 1e-6 against the oracle on
+            # those very samples; the generator then restores the chunk bit for bit
+            x.add_(1e3 + 1e-3 * torch.arange(length, dtype=torch.float64, device="cuda"))
+            f.apply_batch(x, z, chunk, length, dtype="f64", rel_tol=1e-6)
+            torch.cuda.synchronize()
+            check(normwise(z[sample].cpu().numpy(), of.apply_f64(x[sample].cpu().numpy())), 1e-6, ("config 5 full slice, tolerance call, 1e3 + 1e-3 t", c0))
+            sg.synth(x, channel0=c0)
             del z
             checked += 1
     assert checked == 2
