@@ -190,33 +190,170 @@ bool filter_sane(const SavgolFilter *f, const char *who)
 // sub-rows by enqueue_long below -- the reference's savgol_apply takes a size_t length
 constexpr size_t LAUNCH_MAX_LENGTH = (size_t)1 << 30;
 
-// Job1D::xcd_chunk_log2 of the tile kernels (SAVGOL_HIP_1D_XCD_CHUNK_LOG2, default 6; see enqueue_batch)
-unsigned xcd_chunk_log2()
+// ------------------------------------------------------------------------------------------------
+// The decisions every device route shares, each stated here and nowhere else: the argument checks, what a call stores where
+// (CallShape), what one output adds to it (OutputPart), which kernel family and tile width a call takes, how a batch is cut
+// into launches.  enqueue_multi and enqueue_h16 promise the bits of enqueue_batch<float>: they hold because all three ask these.
+// ------------------------------------------------------------------------------------------------
+
+// The argument checks of a batch call, in this order.  `too_long`: the refusal text (who, length) of a route that does not serve
+// channels beyond LAUNCH_MAX_LENGTH, NULL where enqueue_long takes them.
+bool check_rows(const char *who, const SavgolFilter *f, const void *d_in, const void *d_out, size_t length, size_t in_ld, size_t out_ld, Variant variant,
+                const char *too_long = nullptr)
 {
-    static const unsigned xcd_chunk_env = [] { const char *e = getenv("SAVGOL_HIP_1D_XCD_CHUNK_LOG2"); return e ? (unsigned)atoi(e) : 6u; }();
-    return xcd_chunk_env;
+    if (!f || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return false; }
+    if (!filter_sane(f, who)) return false;
+    const int n = f->config.half_window, ws = f->window_size;
+    if (length < (size_t)ws) { sg_set_error("%s: data length (%zu) < window size (%d)", who, length, ws); return false; }
+    if (too_long && length > LAUNCH_MAX_LENGTH) { sg_set_error(too_long, who, length); return false; }
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
+    if (in_ld < length || out_ld < out_len) { sg_set_error("%s: row pitch smaller than the row", who); return false; }
+    return true;
 }
+
+// Two pitched row sets [base + c pitch, base + c pitch + len), everything in bytes: do any two rows share a byte?  The extents may
+// interleave (in = buf[:, 0, :], out = buf[:, 1, :] with both pitches 2 L) without any row touching another.
+bool rows_overlap_bytes(uintptr_t a0, size_t a_pitch, size_t a_len, uintptr_t b0, size_t b_pitch, size_t b_len, size_t channels)
+{
+    const uintptr_t a1 = a0 + (channels - 1) * a_pitch + a_len, b1 = b0 + (channels - 1) * b_pitch + b_len;
+    if (!(a0 < b1 && b0 < a1)) return false;                       // the whole extents are disjoint: the common case
+    if (a_pitch != b_pitch || channels == 1) return true;
+    // equal pitches: row i of one buffer can only meet rows of the other that start within one pitch of it.  `a` rows occupy
+    // [0, a_len) mod pitch, `b` rows [d, d + b_len) mod pitch
+    const uintptr_t d = a0 <= b0 ? (b0 - a0) % a_pitch : (a_pitch - (a0 - b0) % a_pitch) % a_pitch;      // offset of a `b` row inside a's pitch
+    return d < a_len || d + b_len > a_pitch;
+}
+template <typename T>
+bool rows_overlap(const T *d_in, size_t in_ld, size_t in_len, const T *d_out, size_t out_ld, size_t out_len, size_t channels)
+{
+    return rows_overlap_bytes((uintptr_t)d_in, in_ld * sizeof(T), in_len * sizeof(T), (uintptr_t)d_out, out_ld * sizeof(T), out_len * sizeof(T), channels);
+}
+
+// the boundary mode a variant runs with
+inline int boundary_mode(const SavgolFilter *f, Variant variant)
+{
+    return (variant == FULL) ? (int)f->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
+}
+
+// What a call does to every row, from (filter, variant, length): the mode byte of Job1D::flags, whether the POLYNOMIAL edge rows
+// ride along, which samples the centre kernel stores and where.
+struct CallShape {
+    int      mode;
+    bool     poly, want_edges;
+    unsigned mode_flags;                    // the low byte of the job's flags
+    unsigned store_lo, store_hi, out_shift;
+};
+CallShape call_shape(const SavgolFilter *f, Variant variant, size_t length)
+{
+    const unsigned n = f->config.half_window;
+    CallShape c;
+    c.mode = boundary_mode(f, variant);
+    c.poly = c.mode == SAVGOL_BOUNDARY_POLYNOMIAL;
+    c.want_edges = c.poly && (variant == FULL || variant == FULL_POLY_EDGES);
+    c.mode_flags = (c.mode < 0 || c.mode > 255) ? 255u : ((unsigned)c.mode & sg::JOB_MODE_MASK);     // unknown mode: zero padding (reference :478-480)
+    // the centre kernel stores the interior when edge rows / VALID take the rest (INTERIOR runs as poly without the edge rows)
+    const bool interior_only = (variant == VALID) || c.poly;
+    c.store_lo = interior_only ? n : 0u;
+    c.store_hi = interior_only ? (unsigned)(length - n) : (unsigned)length;
+    c.out_shift = (variant == VALID) ? n : 0u;
+    return c;
+}
+
+// every group of E elements the tile kernels move as one vector is naturally aligned (JOB_VEC_IN; JOB_VEC_OUT with the output's shift)
+inline bool rows_vector_aligned(const void *base, size_t ld, size_t elem_bytes, unsigned E, unsigned shift = 0)
+{
+    return (uintptr_t)base % (E * elem_bytes) == 0 && ld % E == 0 && shift % E == 0;
+}
+
+// What one output adds: Job1D's dt_inv, centre_sum and the JOB_SCALE | JOB_VEC_OUT | JOB_CENTRE | JOB_EDGE_NEGATE bits (the arrays of JobMulti1D).
+// `centred`: fp32 arithmetic, where derivative filters run on centred tiles (sg1d_tile_body, JOB_CENTRE): what a constant comes out as, before
+// dt_inv, is taken from the reference's own table.
+struct OutputPart { float dt_inv, centre_sum; unsigned flags; };
+OutputPart output_part(const SavgolFilter *f, const CallShape &c, unsigned flags, bool centred, bool vec_out)
+{
+    OutputPart o{dt_inverse(f), 0.0f, 0u};
+    if (o.dt_inv != 1.0f) o.flags |= sg::JOB_SCALE;
+    if (vec_out) o.flags |= sg::JOB_VEC_OUT;
+    if (centred && f->config.derivative >= 1) {
+        double wsum = 0.0;
+        for (int k = 0; k <= 2 * f->config.half_window; ++k) wsum += (double)f->center_weights[k];
+        o.centre_sum = (float)wsum;
+        o.flags |= sg::JOB_CENTRE;
+    }
+    if (c.want_edges && (flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) && (f->config.derivative & 1)) o.flags |= sg::JOB_EDGE_NEGATE;
+    return o;
+}
+
+// The geometry and the shared fields of a tile job: TW samples per tile, the input rows, the stored range, the mode byte.
+void job_init(sg::Job1D &job, const CallShape &c, size_t length, size_t in_ld, size_t out_ld, unsigned TW, bool vec_in)
+{
+    memset(&job, 0, sizeof(job));
+    // Tile order: chunks of 64 blocks dealt to the XCDs round robin (round 5; until then every XCD swept one contiguous eighth of the tiles, its
+    // front gigabytes away from the other seven).  Sampled over fresh placements of the two buffers inside one process, columns rotated
+    // (tools/placement_1d.py, profiles/r05_placement_1d.txt): headline shape 5.53 against 5.65 ms median, ahead on every one of six buffer pairs; chunks
+    // of 32 / 256 / 1024 blocks 5.64 / 5.60 / 5.60; launch order loses 15 %.  SAVGOL_HIP_1D_XCD_CHUNK_LOG2=0 is the old order.
+    static const unsigned xcd_chunk_env = [] { const char *e = getenv("SAVGOL_HIP_1D_XCD_CHUNK_LOG2"); return e ? (unsigned)atoi(e) : 6u; }();
+    job.xcd_chunk_log2 = xcd_chunk_env;
+    job.in_ld = (long long)in_ld;
+    job.out_ld = (long long)out_ld;
+    job.length = (unsigned)length;
+    sg::set_tiles_per_channel(job, (unsigned)((length + TW - 1) / TW));
+    job.store_lo = c.store_lo;
+    job.store_hi = c.store_hi;
+    job.out_shift = c.out_shift;
+    job.flags = c.mode_flags | (vec_in ? sg::JOB_VEC_IN : 0u);
+}
+// one output's part and its edge rows into a single-output job
+void job_set_output(sg::Job1D &job, const OutputPart &o, const float *d_edges)
+{
+    job.dt_inv = o.dt_inv;
+    job.centre_sum = o.centre_sum;
+    job.flags |= o.flags;
+    job.edges = d_edges;            // the POLYNOMIAL edge rows ride in the same launch: two more items per channel behind the tiles (sg1d_edge_item)
+}
+
+// Does an fp32-arithmetic call take the half-lane block-moment kernels (where the fit accepts the table)?  Only where they cost no accuracy (round 4,
+// tools/diag_1d_accuracy.py): the block's sum is the largest single term of an output, so where the filter nulls the signal -- moving averages
+// (poly_order 0, 1) on a tone, second derivatives -- its rounding shows: 1.5-2.9 x the reference's own fp32 error there, <= 1.3 x for poly_order >= 2
+// with derivative <= 1 (every half window 24..32, all boundary modes; the plain three-chain kernel: 0.7-1.3 x everywhere).  Those filters take the
+// plain kernel (8 % slower).
+bool takes_moment32(const SavgolFilter *f, int n, unsigned flags)
+{
+    const bool moment_safe = f->config.poly_order >= 2 && f->config.derivative <= 1;
+    return !(flags & (SAVGOL_BATCH_REFERENCE_SUMMATION | SAVGOL_BATCH_PLAIN_SUMMATION)) && n >= sg::MOMENTH_MIN_N && n <= sg::MOMENT_MAX_N && moment_safe;
+}
+
+// Does a single call on the plain kernels take the wide tile?  Where one is built, and the batch is big enough to keep the chip in whole rounds of
+// them or the caller says so.  (The moment kernels are laid out for 8 vectors per lane: a call that takes them stays narrow whatever this says.)
+bool single_takes_wide(size_t elem, int n, unsigned flags, size_t channels, size_t length)
+{
+    const int vpl_wide = sg::wide_vectors_per_lane(elem, n);
+    if (vpl_wide == sg::vectors_per_lane(elem, n) || (flags & SAVGOL_BATCH_TILE_NARROW)) return false;
+    const size_t TW = 64u * (size_t)vpl_wide * (16 / elem);
+    return (flags & SAVGOL_BATCH_TILE_WIDE) || (unsigned long long)channels * ((length + TW - 1) / TW) >= sg::WIDE_TILE_MIN_TILES;
+}
+
+// Launch geometry: one tile (or edge item) per wave, four waves per block, the block count a multiple of 8 for the XCD remap; a launch stays below
+// 2^24 blocks, so a batch is cut into groups of channels -- `for (ChannelGroups g{channels, max}; g.next();)`.
+inline unsigned grid_blocks(unsigned items) { return ((items + 3u) / 4u + 7u) & ~7u; }
+inline size_t launch_max_channels(unsigned tiles_per_channel, unsigned edge_items_per_channel)
+{
+    return (size_t)sg::MAX_TILES_PER_LAUNCH / ((size_t)tiles_per_channel + edge_items_per_channel);
+}
+struct ChannelGroups {
+    size_t channels, max_ch, c0 = 0, nc = 0;        // the group is [c0, c0 + nc)
+    bool next() { c0 += nc; nc = std::min(max_ch, channels - std::min(c0, channels)); return nc != 0; }
+};
+
+// the block-moment launchers by term count (3, 5, 7)
+inline int terms_slot(int terms) { return terms == 3 ? 0 : terms == 5 ? 1 : 2; }
+int (*const MOMENT_F32[3])(int, const sg::Job1D *, const float *, unsigned, void *) = {sg1d_launch_f32_momenth_t3, sg1d_launch_f32_momenth_t5, sg1d_launch_f32_momenth_t7};
+int (*const MOMENT_F64[3])(int, const sg::Job1D *, const double *, unsigned, void *) = {sg1d_launch_f64_moment_t3, sg1d_launch_f64_moment_t5, sg1d_launch_f64_moment_t7};
+int (*const MOMENT_H16[3])(int, const sg::JobH16 *, const float *, unsigned, void *) = {sg1d_launch_h16_momenth_t3, sg1d_launch_h16_momenth_t5, sg1d_launch_h16_momenth_t7};
 
 template <typename T>
 int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out, size_t channels, size_t length,
                  size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags);
-
-// d_in / d_out as pitched row sets [base + c ld, base + c ld + len): do any two rows share a byte?  The extents may interleave
-// (in = buf[:, 0, :], out = buf[:, 1, :] with both pitches 2 L) without any row touching another.
-template <typename T>
-bool rows_overlap(const T *d_in, size_t in_ld, size_t in_len, const T *d_out, size_t out_ld, size_t out_len, size_t channels)
-{
-    const uintptr_t a0 = (uintptr_t)d_in, a1 = a0 + ((channels - 1) * in_ld + in_len) * sizeof(T);
-    const uintptr_t b0 = (uintptr_t)d_out, b1 = b0 + ((channels - 1) * out_ld + out_len) * sizeof(T);
-    if (!(a0 < b1 && b0 < a1)) return false;                       // the whole extents are disjoint: the common case
-    if (in_ld != out_ld || channels == 1) return true;
-    // equal pitches: row i of one buffer can only meet rows of the other that start within one pitch of it
-    const uintptr_t pitch = in_ld * sizeof(T);
-    const uintptr_t d = a0 <= b0 ? (b0 - a0) % pitch : (pitch - (a0 - b0) % pitch) % pitch;      // offset of an output row inside the input's pitch
-    // input rows occupy [0, in_len) mod pitch, output rows [d, d + out_len) mod pitch
-    const uintptr_t il = in_len * sizeof(T), ol = out_len * sizeof(T);
-    return d < il || d + ol > pitch;
-}
 
 // a stream-ordered scratch block that every exit hands back (the error returns of the in-place call leaked its stash)
 template <typename T>
@@ -225,20 +362,19 @@ struct ScratchGuard {
     ~ScratchGuard() { if (armed && p) (void)sg::scratch_free(p, st, "scratch free (in-place stash, error exit)"); }
 };
 
+// ------------------------------------------------------------------------------------------------
+// enqueue one batch
+// ------------------------------------------------------------------------------------------------
 template <typename T>
 int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_out, size_t channels, size_t length,
                   size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
 {
     const bool reference_order = sizeof(T) == 4 && (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) != 0;
-    const bool correct_edge = (flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) != 0;
-    if (!f || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
-    if (!filter_sane(f, who)) return -1;
-    const int n = f->config.half_window, ws = f->window_size;
-    if (length < (size_t)ws) { sg_set_error("%s: data length (%zu) < window size (%d)", who, length, ws); return -1; }
-    if (length > LAUNCH_MAX_LENGTH) return enqueue_long<T>(who, f, d_in, d_out, channels, length, in_ld, out_ld, variant, st, flags);
-    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
-    if (in_ld < length || out_ld < out_len) { sg_set_error("%s: row pitch smaller than the row", who); return -1; }
+    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant)) return -1;
     if (channels == 0) return 0;
+    if (length > LAUNCH_MAX_LENGTH) return enqueue_long<T>(who, f, d_in, d_out, channels, length, in_ld, out_ld, variant, st, flags);
+    const int n = f->config.half_window, ws = f->window_size;
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
     // IN PLACE (round 5; the reference advertises output == input, include/iterative/savgolFilter.h:148): exactly the same
     // rows -- same base, same pitch, the full-length variants -- run on the tile kernels with every tile's halo taken from a stash that is
     // filled first (3 % of the data at n = 32), and give the OUT-OF-PLACE answer, not the reference's own in-place result (which reads samples it
@@ -251,16 +387,8 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
 
     DeviceCtx *ctx = sg::ctx_get();
     if (!ctx) return -1;
-    const int mode = (variant == FULL) ? (int)f->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
-    const bool poly = (mode == SAVGOL_BOUNDARY_POLYNOMIAL);
-    const bool want_edges = poly && variant != VALID && variant != INTERIOR;
-    // Block moments only where they cost no accuracy (round 4, tools/diag_1d_accuracy.py): the block's sum is the largest single term of
-    // an output, so where the filter nulls the signal -- moving averages (poly_order 0, 1) on a tone, second derivatives -- its rounding
-    // shows: 1.5-2.9 x the reference's own fp32 error there, <= 1.3 x for poly_order >= 2 with derivative <= 1 (every half window
-    // 24..32, all boundary modes; the plain three-chain kernel: 0.7-1.3 x everywhere).  Those filters take the plain kernel (8 % slower).
-    const bool moment_safe = f->config.poly_order >= 2 && f->config.derivative <= 1;
-    const bool want_moment = sizeof(T) == 4 && !reference_order && n >= sg::MOMENTH_MIN_N && n <= sg::MOMENT_MAX_N &&
-                             !(flags & SAVGOL_BATCH_PLAIN_SUMMATION) && moment_safe;
+    const CallShape shape = call_shape(f, variant, length);
+    const bool want_moment = sizeof(T) == 4 && takes_moment32(f, n, flags);
     // fp64, half windows 24..32, on request only: block moments (sg_k1d_moment64.hpp) -- within ~1e-7 of the default path, not its 1e-12
     const bool want_moment64 = sizeof(T) == 8 && (flags & SAVGOL_BATCH_MOMENT_F64) && n >= sg::MOMENT_MIN_N && n <= sg::MOMENT_MAX_N;
     if (inplace && reference_order) {
@@ -272,18 +400,17 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
         if (!sg::scratch_free(copy, st, "scratch free (in-place copy)")) rc = -1;
         return rc;
     }
-    const FilterPlan *plan = plan_get(ctx, f, reference_order ? NEED_REF : ((want_edges ? NEED_EDGES : 0u) | (want_moment ? NEED_MOMENT : 0u) | (want_moment64 ? NEED_MOMENT64 : 0u)));
+    const FilterPlan *plan = plan_get(ctx, f, reference_order ? NEED_REF : ((shape.want_edges ? NEED_EDGES : 0u) | (want_moment ? NEED_MOMENT : 0u) | (want_moment64 ? NEED_MOMENT64 : 0u)));
     if (!plan) return -1;
 
     if constexpr (sizeof(T) == 4) {
         if (reference_order) {
             // one output per thread in the reference's own summation order: bit-identical to its savgol_apply
             const float *d_table = plan->d_ref;
-            const int rmode = mode;
-            const bool inner = variant == VALID || variant == INTERIOR;                 // no edge outputs at all
+            const int rmode = shape.mode, shift = (int)shape.out_shift;
+            const bool poly = shape.poly, inner = variant == VALID || variant == INTERIOR;                 // inner: no edge outputs at all
             const int lo = inner ? n : 0, hi = inner ? (int)length - n : (int)length;
-            const int shift = (variant == VALID) ? n : 0;
-            const int negate = (poly && correct_edge && (f->config.derivative & 1)) ? 1 : 0;
+            const int negate = (poly && (flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) && (f->config.derivative & 1)) ? 1 : 0;
             int rc;
             if (channels * length >= ((size_t)1 << 16) && length >= (size_t)4 * ws) {
                 // long batches: the packed kernel for everything the centre taps produce, the per-thread kernel for
@@ -308,46 +435,16 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
     }
 
     constexpr int E = 16 / (int)sizeof(T);
-    // tile width: the wide tile where one is built and the batch is big enough to keep the chip in whole rounds of them
-    int vpl = sg::vectors_per_lane(sizeof(T), f->config.half_window);
-    const int vpl_wide = sg::wide_vectors_per_lane(sizeof(T), f->config.half_window);
-    const int tile_mode = (flags & SAVGOL_BATCH_TILE_NARROW) ? 1 : ((flags & SAVGOL_BATCH_TILE_WIDE) ? 2 : 0);
-    const int wide = vpl_wide != vpl && tile_mode != 1 && !(want_moment64 && plan->moment64_terms > 0 && plan->sym) &&       // (the moment kernels are laid out for 8 vectors per lane)
-                     !(want_moment && plan->moment_terms > 0) &&
-                     (tile_mode == 2 || (unsigned long long)channels * ((length + 64u * vpl_wide * E - 1) / (64u * vpl_wide * E)) >= sg::WIDE_TILE_MIN_TILES);
-    if (wide) vpl = vpl_wide;
-    const unsigned TW = 64u * (unsigned)vpl * E;
+    // the kernel family: block moments replace the taps on the lanes' common block when the table is a polynomial (a table that is not keeps the plain kernel)
+    const float *d_moment = (want_moment && plan->moment_terms > 0) ? plan->d_moment : nullptr;
+    const double *d_moment64 = (want_moment64 && plan->moment64_terms > 0 && plan->sym) ? plan->d_moment64 : nullptr;
+    const int wide = !d_moment && !d_moment64 && single_takes_wide(sizeof(T), n, flags, channels, length);
+    const unsigned TW = 64u * (unsigned)(wide ? sg::wide_vectors_per_lane(sizeof(T), n) : sg::vectors_per_lane(sizeof(T), n)) * E;
 
     sg::Job1D job;
-    memset(&job, 0, sizeof(job));
-    // Tile order: chunks of 64 blocks dealt to the XCDs round robin (round 5; until then every XCD swept one contiguous eighth of the tiles, its
-    // front gigabytes away from the other seven).  Sampled over fresh placements of the two buffers inside one process, columns rotated
-    // (tools/placement_1d.py, profiles/r05_placement_1d.txt): headline shape 5.53 against 5.65 ms median, ahead on every one of six buffer pairs; chunks
-    // of 32 / 256 / 1024 blocks 5.64 / 5.60 / 5.60; launch order loses 15 %.  SAVGOL_HIP_1D_XCD_CHUNK_LOG2=0 is the old order.
-    job.xcd_chunk_log2 = xcd_chunk_log2();
-    job.in_ld = (long long)in_ld;
-    job.out_ld = (long long)out_ld;
-    job.length = (unsigned)length;
-    sg::set_tiles_per_channel(job, (unsigned)((length + TW - 1) / TW));
-    job.dt_inv = dt_inverse(f);
-    // which samples the centre kernel stores: the interior when edge rows / VALID take the rest
-    const bool interior_only = (variant == VALID) || poly;              // INTERIOR runs as poly without the edge rows
-    job.store_lo = interior_only ? (unsigned)n : 0u;
-    job.store_hi = interior_only ? (unsigned)(length - n) : (unsigned)length;
-    job.out_shift = (variant == VALID) ? (unsigned)n : 0u;
-    job.flags = ((unsigned)mode & sg::JOB_MODE_MASK);
-    if (mode < 0 || mode > 255) job.flags = 255u;                       // unknown mode: zero padding (reference :478-480)
-    if (job.dt_inv != 1.0f) job.flags |= sg::JOB_SCALE;
-    if (((uintptr_t)d_in % 16 == 0) && (in_ld % E == 0)) job.flags |= sg::JOB_VEC_IN;
-    if (((uintptr_t)d_out % 16 == 0) && (out_ld % E == 0) && (job.out_shift % E == 0)) job.flags |= sg::JOB_VEC_OUT;
-    if (sizeof(T) == 4 && f->config.derivative >= 1) {
-        // fp32 derivative filters run on centred tiles (sg1d_tile_body, JOB_CENTRE): what a constant comes out as is taken from the reference's own table
-        double wsum = 0.0;
-        for (int k = 0; k <= 2 * n; ++k) wsum += (double)f->center_weights[k];
-        job.centre_sum = (float)wsum;
-        job.flags |= sg::JOB_CENTRE;
-    }
-
+    job_init(job, shape, length, in_ld, out_ld, TW, rows_vector_aligned(d_in, in_ld, sizeof(T), E));
+    const float *d_edges = shape.want_edges ? plan->d_edges : nullptr;
+    job_set_output(job, output_part(f, shape, flags, sizeof(T) == 4, rows_vector_aligned(d_out, out_ld, sizeof(T), E, shape.out_shift)), d_edges);
     if (sizeof(T) == 8) {
         if (!plan->sym) {
             sg_set_error("%s: fp64 path needs the centre taps savgol_create builds (tap[k] == %stap[2n-k]); tap %d is not", who,
@@ -357,19 +454,8 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
         if (plan->odd) job.flags |= sg::JOB_ODD_TAPS;
     }
     const sg::Taps &taps = sizeof(T) == 8 ? plan->taps64 : plan->taps32;
-    const float *d_edges = want_edges ? plan->d_edges : nullptr;
-    // half windows 24..32, fp32: block moments replace the taps on the lanes' common block when the table is a polynomial
-    const float *d_moment = (want_moment && plan->moment_terms > 0) ? plan->d_moment : nullptr;
-    const int moment_terms = d_moment ? plan->moment_terms : 0;
-    const double *d_moment64 = (want_moment64 && plan->moment64_terms > 0 && plan->sym) ? plan->d_moment64 : nullptr;     // a table that is not a polynomial keeps the plain kernel
 
-    // the POLYNOMIAL edge rows ride in the same launch: two more items per channel behind the tiles (sg1d_edge_item)
-    if (d_edges) {
-        job.edges = d_edges;
-        if (correct_edge && (f->config.derivative & 1)) job.flags |= sg::JOB_EDGE_NEGATE;
-    }
-    // split so that a launch stays below 2^24 blocks of four tiles (sg::MAX_TILES_PER_LAUNCH)
-    size_t max_ch = (size_t)sg::MAX_TILES_PER_LAUNCH / ((size_t)job.tiles_per_channel + 2);
+    size_t max_ch = launch_max_channels(job.tiles_per_channel, 2);
     if (inplace) {
         // in place: channel groups whose stash (one slot of 2 NA samples per ODD tile + 4 NA per channel) stays below 3/4 of what the scratch pool keeps
         // (192 of 256 MiB by default; SAVGOL_HIP_SCRATCH_KEEP_MB moves both), so it is neither handed back to the driver nor mapped again from call to call
@@ -384,18 +470,9 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
     }
     // the tile launch of the chosen kernel family: one tile per wave, blocks dispatched in order (see sg1d_center_kernel)
     auto launch_tiles = [&](const sg::Job1D &j) -> int {
-        unsigned blocks = (j.total_tiles + j.edge_items + 3u) / 4u;
-        blocks = (blocks + 7u) & ~7u;                                    // the XCD remap wants a multiple of 8
-        if (d_moment)
-            return moment_terms == 3 ? sg1d_launch_f32_momenth_t3(n, &j, d_moment, blocks, st)
-                 : moment_terms == 5 ? sg1d_launch_f32_momenth_t5(n, &j, d_moment, blocks, st)
-                                     : sg1d_launch_f32_momenth_t7(n, &j, d_moment, blocks, st);
-        if (d_moment64) {
-            const int mt = plan->moment64_terms;
-            return mt == 3 ? sg1d_launch_f64_moment_t3(n, &j, d_moment64, blocks, st)
-                 : mt == 5 ? sg1d_launch_f64_moment_t5(n, &j, d_moment64, blocks, st)
-                           : sg1d_launch_f64_moment_t7(n, &j, d_moment64, blocks, st);
-        }
+        const unsigned blocks = grid_blocks(j.total_tiles + j.edge_items);
+        if (d_moment) return MOMENT_F32[terms_slot(plan->moment_terms)](n, &j, d_moment, blocks, st);
+        if (d_moment64) return MOMENT_F64[terms_slot(plan->moment64_terms)](n, &j, d_moment64, blocks, st);
         return sg::launch_center<T>(n, wide, j, taps, blocks, st);
     };
     const unsigned tpc = job.tiles_per_channel;
@@ -406,8 +483,8 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
         if (!edge_all) return -1;
     }
     ScratchGuard<T> edge_guard{edge_all, st, edge_all != nullptr};
-    for (size_t c0 = 0; c0 < channels; c0 += max_ch) {
-        const size_t nc = (channels - c0 < max_ch) ? channels - c0 : max_ch;
+    for (ChannelGroups g{channels, max_ch}; g.next();) {
+        const size_t c0 = g.c0, nc = g.nc;
         job.in = d_in + c0 * in_ld;
         job.out = d_out + c0 * out_ld;
         if (!inplace) {
@@ -447,16 +524,13 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
     }
     if (inplace && edge_all) {
         // every channel's two edge items, 2^22 items (two million channels) per launch
-        for (size_t c0 = 0; c0 < channels; c0 += (size_t)1 << 21) {
-            const size_t nc = channels - c0 < ((size_t)1 << 21) ? channels - c0 : ((size_t)1 << 21);
+        for (ChannelGroups g{channels, (size_t)1 << 21}; g.next();) {
             sg::Job1D ej = job;
-            ej.in = d_in + c0 * in_ld;
-            ej.out = d_out + c0 * out_ld;
-            ej.edge_stash = edge_all + c0 * 2 * (size_t)ws;
-            ej.total_tiles = 0; ej.edge_items = (unsigned)(2 * nc);
-            unsigned eb = (ej.edge_items + 3u) / 4u;
-            eb = (eb + 7u) & ~7u;
-            if (sg::launch_center<T>(n, 0, ej, taps, eb, st) != 0) return -1;
+            ej.in = d_in + g.c0 * in_ld;
+            ej.out = d_out + g.c0 * out_ld;
+            ej.edge_stash = edge_all + g.c0 * 2 * (size_t)ws;
+            ej.total_tiles = 0; ej.edge_items = (unsigned)(2 * g.nc);
+            if (sg::launch_center<T>(n, 0, ej, taps, grid_blocks(ej.edge_items), st) != 0) return -1;
         }
         edge_guard.armed = false;
         if (!sg::scratch_free(edge_all, st, "scratch free (in-place edge samples)")) return -1;
@@ -465,9 +539,9 @@ int enqueue_batch(const char *who, const SavgolFilter *f, const T *d_in, T *d_ou
 }
 
 // ------------------------------------------------------------------------------------------------
-// Channels longer than LAUNCH_MAX_LENGTH samples (the reference's savgol_apply takes any size_t length, savgolFilter.c:743-766).
-// Outputs [n, L-n) do not depend on the boundary mode: they are enqueued as sub-rows [a-n, b+n) of at most 2^29 + 2n samples
-// through the same kernels (what lies beyond a sub-row only reaches outputs it does not store).  The 2n edge outputs of a
+// Channels longer than LAUNCH_MAX_LENGTH samples (the reference's savgol_apply takes any size_t length, savgolFilter.c:743-766); enqueue_batch
+// has checked the arguments.  Outputs [n, L-n) do not depend on the boundary mode: they are enqueued as sub-rows [a-n, b+n) of at most 2^29 + 2n
+// samples through the same kernels (what lies beyond a sub-row only reaches outputs it does not store).  The 2n edge outputs of a
 // channel only see the 3n samples next to them -- or, PERIODIC, the other end of the channel -- so they are computed on two
 // 256-sample copies of the channel ends (one ring of both ends for PERIODIC) and copied into place: same arithmetic per
 // output as the unsplit call, in every summation mode.  Everything is enqueued on `st`; the scratch is stream-ordered.
@@ -478,8 +552,6 @@ int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out
 {
     const size_t n = (size_t)f->config.half_window;
     const size_t out_len = (variant == VALID) ? length - 2 * n : length;
-    if (in_ld < length || out_ld < out_len) { sg_set_error("%s: row pitch smaller than the row", who); return -1; }
-    if (channels == 0) return 0;
     if (rows_overlap(d_in, in_ld, length, d_out, out_ld, out_len, channels)) { sg_set_error("%s: d_in and d_out overlap (channels longer than 2^30 samples run out of place only: include/savgol_hip.h, in-place contract)", who); return -1; }
     constexpr size_t SEG = (size_t)1 << 29;                       // outputs per sub-row (a multiple of the vector width: sub-rows stay 16-byte aligned)
     for (size_t a = n; a < length - n; a += SEG) {
@@ -491,11 +563,9 @@ int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out
     if (variant == VALID || variant == INTERIOR) return 0;
 
     constexpr size_t E = 256;                                    // samples of a channel end that are copied out (>= 4 half windows, vector aligned)
-    const int mode = (variant == FULL) ? (int)f->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
-    T *scratch = nullptr;
-    DeviceCtx *ctx_long = sg::ctx_get();
-    if (!ctx_long) return -1;
-    scratch = static_cast<T *>(sg::scratch_alloc(ctx_long, 4 * channels * E * sizeof(T), st, "scratch (channel ends)"));
+    DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    T *scratch = static_cast<T *>(sg::scratch_alloc(ctx, 4 * channels * E * sizeof(T), st, "scratch (channel ends)"));
     if (!scratch) return -1;
     T *in_a = scratch, *in_b = scratch + channels * E, *out_a = scratch + 2 * channels * E, *out_b = scratch + 3 * channels * E;
     auto copy2d = [&](T *dst, size_t dst_ld, const T *src, size_t src_ld, size_t width) {
@@ -503,7 +573,7 @@ int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out
                           "hipMemcpy2DAsync(channel ends)");
     };
     bool ok;
-    if (mode == (int)SAVGOL_BOUNDARY_PERIODIC) {
+    if (boundary_mode(f, variant) == (int)SAVGOL_BOUNDARY_PERIODIC) {
         // ring of both ends: [in[L-128 .. L), in[0 .. 128)]; its interior outputs 128-n .. 128+n-1 are the channel's L-n .. L-1, 0 .. n-1
         ok = copy2d(in_a, E, d_in + (length - E / 2), in_ld, E / 2) && copy2d(in_a + E / 2, E, d_in, in_ld, E / 2) &&
              enqueue_batch<T>(who, f, in_a, out_a, channels, E, E, E, INTERIOR, st, flags) == 0 &&
@@ -536,7 +606,7 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
         if (!filter_sane(filters[k], who)) return -1;
     }
     const SavgolFilter *f0 = filters[0];
-    const int n = f0->config.half_window, ws = f0->window_size;
+    const int n = f0->config.half_window;
     for (int k = 1; k < count; ++k) {
         if (filters[k]->config.half_window != n) {
             sg_set_error("%s: filters[%d] has half_window %d, filters[0] %d (all filters need the same half_window)", who, k, (int)filters[k]->config.half_window, n);
@@ -548,10 +618,9 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
             return -1;
         }
     }
-    if (length < (size_t)ws) { sg_set_error("%s: data length (%zu) < window size (%d)", who, length, ws); return -1; }
-    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
-    if (in_ld < length || out_ld < out_len) { sg_set_error("%s: row pitch smaller than the row", who); return -1; }
+    if (!check_rows(who, f0, d_in, d_outs[0], length, in_ld, out_ld, variant)) return -1;
     if (channels == 0) return 0;
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
     for (int k = 0; k < count; ++k) {
         if (rows_overlap(d_in, in_ld, length, static_cast<const float *>(d_outs[k]), out_ld, out_len, channels)) {
             sg_set_error("%s: d_outs[%d] overlaps d_in (the multi-output call does not run in place)", who, k);
@@ -571,12 +640,7 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
             if (single(k) != 0) return -1;
         return 0;
     }
-    // the tile the single calls take (enqueue_batch with plain summation: no moment kernels)
-    constexpr unsigned E = 4;
-    const int vpl = sg::VPL_NARROW, vpl_wide = sg::wide_vectors_per_lane(sizeof(float), n);
-    const int tile_mode = (flags & SAVGOL_BATCH_TILE_NARROW) ? 1 : ((flags & SAVGOL_BATCH_TILE_WIDE) ? 2 : 0);
-    const bool single_wide = vpl_wide != vpl && tile_mode != 1 &&
-                             (tile_mode == 2 || (unsigned long long)channels * ((length + 64u * vpl_wide * E - 1) / (64u * vpl_wide * E)) >= sg::WIDE_TILE_MIN_TILES);
+    const bool single_wide = single_takes_wide(sizeof(float), n, single_flags, channels, length);
     int fused[SAVGOL_MULTI_MAX_FILTERS], nf = 0;
     for (int k = 0; k < count; ++k) {
         if (single_wide && filters[k]->config.derivative >= 1) { if (single(k) != 0) return -1; }
@@ -587,28 +651,12 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
 
     DeviceCtx *ctx = sg::ctx_get();
     if (!ctx) return -1;
-    const int mode = (variant == FULL) ? (int)f0->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
-    const bool poly = mode == SAVGOL_BOUNDARY_POLYNOMIAL;
-    const bool want_edges = poly && variant == FULL;
-    const bool correct_edge = (flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) != 0;
-    const unsigned TW = 64u * (unsigned)vpl * E;
-
+    const CallShape shape = call_shape(f0, variant, length);
+    constexpr unsigned E = 4;
     sg::JobMulti1D jm;
     memset(&jm, 0, sizeof(jm));
-    sg::Job1D &job = jm.base;
-    job.xcd_chunk_log2 = xcd_chunk_log2();
-    job.in_ld = (long long)in_ld;
-    job.out_ld = (long long)out_ld;
-    job.length = (unsigned)length;
-    sg::set_tiles_per_channel(job, (unsigned)((length + TW - 1) / TW));
-    const bool interior_only = (variant == VALID) || poly;
-    job.store_lo = interior_only ? (unsigned)n : 0u;
-    job.store_hi = interior_only ? (unsigned)(length - n) : (unsigned)length;
-    job.out_shift = (variant == VALID) ? (unsigned)n : 0u;
-    job.flags = ((unsigned)mode & sg::JOB_MODE_MASK);
-    if (mode < 0 || mode > 255) job.flags = 255u;
-    if (((uintptr_t)d_in % 16 == 0) && (in_ld % E == 0)) job.flags |= sg::JOB_VEC_IN;
-    const unsigned tpc = job.tiles_per_channel;
+    job_init(jm.base, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, sizeof(float), E));
+    const unsigned tpc = jm.base.tiles_per_channel;
 
     // launches of 3, 2 or 2 + 2 outputs; within a launch the smoothing outputs first (they read the raw slab, sg_k1d_multi.hpp)
     for (int g0 = 0; g0 < nf;) {
@@ -622,38 +670,25 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
         jm.nraw = 0;
         for (int j = 0; j < K; ++j) {
             const SavgolFilter *f = filters[order[j]];
-            const FilterPlan *plan = plan_get(ctx, f, want_edges ? NEED_EDGES : 0u);
+            const FilterPlan *plan = plan_get(ctx, f, shape.want_edges ? NEED_EDGES : 0u);
             if (!plan) return -1;
+            const OutputPart o = output_part(f, shape, flags, true, rows_vector_aligned(d_outs[order[j]], out_ld, sizeof(float), E, shape.out_shift));
             taps.t[j] = plan->taps32;
             jm.out[j] = d_outs[order[j]];
-            jm.edges[j] = want_edges ? plan->d_edges : nullptr;
-            jm.dt_inv[j] = dt_inverse(f);
-            unsigned fl = 0;
-            if (jm.dt_inv[j] != 1.0f) fl |= sg::JOB_SCALE;
-            if (((uintptr_t)d_outs[order[j]] % 16 == 0) && (out_ld % E == 0) && (job.out_shift % E == 0)) fl |= sg::JOB_VEC_OUT;
-            if (f->config.derivative >= 1) {
-                double wsum = 0.0;                                   // as enqueue_batch: what a constant comes out as, before dt_inv
-                for (int t = 0; t <= 2 * n; ++t) wsum += (double)f->center_weights[t];
-                jm.centre_sum[j] = (float)wsum;
-                fl |= sg::JOB_CENTRE;
-            } else {
-                ++jm.nraw;
-            }
-            if (want_edges && correct_edge && (f->config.derivative & 1)) fl |= sg::JOB_EDGE_NEGATE;
-            jm.flags[j] = fl;
+            jm.edges[j] = shape.want_edges ? plan->d_edges : nullptr;
+            jm.dt_inv[j] = o.dt_inv;
+            jm.centre_sum[j] = o.centre_sum;
+            jm.flags[j] = o.flags;
+            if (!(o.flags & sg::JOB_CENTRE)) ++jm.nraw;
         }
-        // a launch stays below 2^24 blocks of four tiles, the edge items of every output counted
-        const size_t max_ch = (size_t)sg::MAX_TILES_PER_LAUNCH / ((size_t)tpc + 2 * (size_t)K);
-        for (size_t c0 = 0; c0 < channels; c0 += max_ch) {
-            const size_t nc = (channels - c0 < max_ch) ? channels - c0 : max_ch;
+        // the edge items of every output counted
+        for (ChannelGroups g{channels, launch_max_channels(tpc, 2 * (unsigned)K)}; g.next();) {
             sg::JobMulti1D j = jm;
-            j.base.in = d_in + c0 * in_ld;
-            for (int o = 0; o < K; ++o) j.out[o] = static_cast<float *>(jm.out[o]) + c0 * out_ld;
-            j.base.total_tiles = (unsigned)(nc * tpc);
-            j.base.edge_items = want_edges ? (unsigned)(2 * nc * (size_t)K) : 0u;
-            unsigned blocks = (j.base.total_tiles + j.base.edge_items + 3u) / 4u;
-            blocks = (blocks + 7u) & ~7u;                                 // the XCD remap wants a multiple of 8
-            if (sg::launch_multi(n, K, j, taps, blocks, st) != 0) return -1;
+            j.base.in = d_in + g.c0 * in_ld;
+            for (int o = 0; o < K; ++o) j.out[o] = static_cast<float *>(jm.out[o]) + g.c0 * out_ld;
+            j.base.total_tiles = (unsigned)(g.nc * tpc);
+            j.base.edge_items = shape.want_edges ? (unsigned)(2 * g.nc * (size_t)K) : 0u;
+            if (sg::launch_multi(n, K, j, taps, grid_blocks(j.base.total_tiles + j.base.edge_items), st) != 0) return -1;
         }
         g0 += K;
     }
@@ -669,16 +704,6 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
 const char *storage_name(int t)
 {
     return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown";
-}
-
-// rows_overlap for buffers of different element sizes: everything in bytes
-bool rows_overlap_bytes(uintptr_t a0, size_t a_pitch, size_t a_len, uintptr_t b0, size_t b_pitch, size_t b_len, size_t channels)
-{
-    const uintptr_t a1 = a0 + (channels - 1) * a_pitch + a_len, b1 = b0 + (channels - 1) * b_pitch + b_len;
-    if (!(a0 < b1 && b0 < a1)) return false;                       // the whole extents are disjoint: the common case
-    if (a_pitch != b_pitch || channels == 1) return true;
-    const uintptr_t d = a0 <= b0 ? (b0 - a0) % a_pitch : (a_pitch - (a0 - b0) % a_pitch) % a_pitch;      // offset of a `b` row inside a's pitch
-    return d < a_len || d + b_len > a_pitch;
 }
 
 int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
@@ -700,14 +725,10 @@ int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in
                      storage_name(in_type), storage_name(out_type), in_type, out_type);
         return -1;
     }
-    if (!f || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
-    if (!filter_sane(f, who)) return -1;
-    const int n = f->config.half_window, ws = f->window_size;
-    if (length < (size_t)ws) { sg_set_error("%s: data length (%zu) < window size (%d)", who, length, ws); return -1; }
-    if (length > LAUNCH_MAX_LENGTH) { sg_set_error("%s: channels longer than 2^30 samples (%zu) are not served on 16-bit storage", who, length); return -1; }
-    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
-    if (in_ld < length || out_ld < out_len) { sg_set_error("%s: row pitch smaller than the row", who); return -1; }
+    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, "%s: channels longer than 2^30 samples (%zu) are not served on 16-bit storage")) return -1;
     if (channels == 0) return 0;
+    const int n = f->config.half_window;
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
     const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
     if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_out, out_ld * ob, out_len * ob, channels)) {
         sg_set_error("%s: d_in and d_out overlap (the 16-bit-storage call does not run in place: input and output rows may not share a byte)", who);
@@ -716,65 +737,28 @@ int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in
 
     DeviceCtx *ctx = sg::ctx_get();
     if (!ctx) return -1;
-    const int mode = (variant == FULL) ? (int)f->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
-    const bool poly = (mode == SAVGOL_BOUNDARY_POLYNOMIAL);
-    const bool want_edges = poly && variant != VALID;
-    // the kernel family enqueue_batch<float> takes: block moments only where they cost no accuracy
-    const bool moment_safe = f->config.poly_order >= 2 && f->config.derivative <= 1;
-    const bool want_moment = n >= sg::MOMENTH_MIN_N && n <= sg::MOMENT_MAX_N && !(flags & SAVGOL_BATCH_PLAIN_SUMMATION) && moment_safe;
-    const FilterPlan *plan = plan_get(ctx, f, (want_edges ? NEED_EDGES : 0u) | (want_moment ? NEED_MOMENT : 0u));
+    const CallShape shape = call_shape(f, variant, length);
+    const bool want_moment = takes_moment32(f, n, flags);
+    const FilterPlan *plan = plan_get(ctx, f, (shape.want_edges ? NEED_EDGES : 0u) | (want_moment ? NEED_MOMENT : 0u));
     if (!plan) return -1;
     const float *d_moment = (want_moment && plan->moment_terms > 0) ? plan->d_moment : nullptr;
 
     constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
-    const unsigned TW = 64u * (unsigned)sg::VPL_NARROW * E;
     sg::JobH16 jh;
     memset(&jh, 0, sizeof(jh));
+    sg::Job1D &job = jh.base;
+    job_init(job, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
+    job_set_output(job, output_part(f, shape, flags, true, rows_vector_aligned(d_out, out_ld, ob, E, shape.out_shift)), shape.want_edges ? plan->d_edges : nullptr);
     jh.in_type = (unsigned)in_type;
     jh.out_type = (unsigned)out_type;
-    sg::Job1D &job = jh.base;
-    job.xcd_chunk_log2 = xcd_chunk_log2();
-    job.in_ld = (long long)in_ld;
-    job.out_ld = (long long)out_ld;
-    job.length = (unsigned)length;
-    sg::set_tiles_per_channel(job, (unsigned)((length + TW - 1) / TW));
-    job.dt_inv = dt_inverse(f);
-    const bool interior_only = (variant == VALID) || poly;
-    job.store_lo = interior_only ? (unsigned)n : 0u;
-    job.store_hi = interior_only ? (unsigned)(length - n) : (unsigned)length;
-    job.out_shift = (variant == VALID) ? (unsigned)n : 0u;
-    job.flags = ((unsigned)mode & sg::JOB_MODE_MASK);
-    if (mode < 0 || mode > 255) job.flags = 255u;
-    if (job.dt_inv != 1.0f) job.flags |= sg::JOB_SCALE;
-    if (((uintptr_t)d_in % (E * ib) == 0) && (in_ld % E == 0)) job.flags |= sg::JOB_VEC_IN;
-    if (((uintptr_t)d_out % (E * ob) == 0) && (out_ld % E == 0) && (job.out_shift % E == 0)) job.flags |= sg::JOB_VEC_OUT;
-    if (f->config.derivative >= 1) {
-        double wsum = 0.0;                                               // as enqueue_batch: what a constant comes out as, before dt_inv
-        for (int k = 0; k <= 2 * n; ++k) wsum += (double)f->center_weights[k];
-        job.centre_sum = (float)wsum;
-        job.flags |= sg::JOB_CENTRE;
-    }
-    if (want_edges) {
-        job.edges = plan->d_edges;
-        if ((flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) && (f->config.derivative & 1)) job.flags |= sg::JOB_EDGE_NEGATE;
-    }
     const unsigned tpc = job.tiles_per_channel;
-    const size_t max_ch = (size_t)sg::MAX_TILES_PER_LAUNCH / ((size_t)tpc + 2);      // a launch stays below 2^24 blocks of four tiles
-    for (size_t c0 = 0; c0 < channels; c0 += max_ch) {
-        const size_t nc = (channels - c0 < max_ch) ? channels - c0 : max_ch;
-        job.in = static_cast<const char *>(d_in) + c0 * in_ld * ib;
-        job.out = static_cast<char *>(d_out) + c0 * out_ld * ob;
-        job.total_tiles = (unsigned)(nc * tpc);
-        job.edge_items = want_edges ? (unsigned)(2 * nc) : 0u;
-        unsigned blocks = (job.total_tiles + job.edge_items + 3u) / 4u;
-        blocks = (blocks + 7u) & ~7u;                                    // the XCD remap wants a multiple of 8
-        int rc;
-        if (d_moment)
-            rc = plan->moment_terms == 3 ? sg1d_launch_h16_momenth_t3(n, &jh, d_moment, blocks, st)
-               : plan->moment_terms == 5 ? sg1d_launch_h16_momenth_t5(n, &jh, d_moment, blocks, st)
-                                         : sg1d_launch_h16_momenth_t7(n, &jh, d_moment, blocks, st);
-        else
-            rc = sg::launch_h16(n, jh, plan->taps32, blocks, st);
+    for (ChannelGroups g{channels, launch_max_channels(tpc, 2)}; g.next();) {
+        job.in = static_cast<const char *>(d_in) + g.c0 * in_ld * ib;
+        job.out = static_cast<char *>(d_out) + g.c0 * out_ld * ob;
+        job.total_tiles = (unsigned)(g.nc * tpc);
+        job.edge_items = shape.want_edges ? (unsigned)(2 * g.nc) : 0u;
+        const unsigned blocks = grid_blocks(job.total_tiles + job.edge_items);
+        const int rc = d_moment ? MOMENT_H16[terms_slot(plan->moment_terms)](n, &jh, d_moment, blocks, st) : sg::launch_h16(n, jh, plan->taps32, blocks, st);
         if (rc != 0) return -1;
     }
     return 0;
@@ -823,7 +807,7 @@ int host_apply_pipelined(const char *who, DeviceCtx *ctx, const SavgolFilter *f,
     const FilterPlan *plan = plan_get(ctx, f, NEED_REF);
     if (!plan) return -1;
     const float *d_table = plan->d_ref;
-    const int mode = (variant == FULL) ? (int)f->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
+    const int mode = boundary_mode(f, variant);
     const int shift = (variant == VALID) ? n : 0;
     const float dt_inv = dt_inverse(f);
 
@@ -948,7 +932,7 @@ static int small_host_call(const char *who, DeviceCtx *ctx, const SavgolFilter *
     const FilterPlan *plan = plan_get(ctx, f, NEED_REF);
     if (!plan) return -1;
     const unsigned flags = host_call_flags();
-    const int mode = (variant == FULL) ? (int)f->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
+    const int mode = boundary_mode(f, variant);
     const bool inner = variant == VALID;
     const int negate = (mode == SAVGOL_BOUNDARY_POLYNOMIAL && (flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) && (f->config.derivative & 1)) ? 1 : 0;
     return sg_small_call(ctx, plan->d_ref, input, output, (int)length, n, mode, inner ? n : 0, inner ? (int)length - n : (int)length, inner ? n : 0, negate,
@@ -1049,32 +1033,29 @@ int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, i
     return enqueue_h16("savgol_apply_valid_batch_h16", filter, d_in, in_type, d_out, out_type, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
 }
 
+// the entry points without flags: their _ex twin on the process defaults (which only ever hold bits flags_ok accepts)
 int savgol_apply_batch_f32(const SavgolFilter *filter, const float *d_in, float *d_out, size_t channels, size_t length,
                            size_t in_ld, size_t out_ld, void *stream)
 {
-    return enqueue_batch<float>("savgol_apply_batch_f32", filter, d_in, d_out, channels, length, in_ld, out_ld, FULL,
-                                static_cast<hipStream_t>(stream), g_default_flags.load());
+    return savgol_apply_batch_f32_ex(filter, d_in, d_out, channels, length, in_ld, out_ld, g_default_flags.load(), stream);
 }
 
 int savgol_apply_batch_f64(const SavgolFilter *filter, const double *d_in, double *d_out, size_t channels, size_t length,
                            size_t in_ld, size_t out_ld, void *stream)
 {
-    return enqueue_batch<double>("savgol_apply_batch_f64", filter, d_in, d_out, channels, length, in_ld, out_ld, FULL,
-                                 static_cast<hipStream_t>(stream), g_default_flags.load());
+    return savgol_apply_batch_f64_ex(filter, d_in, d_out, channels, length, in_ld, out_ld, g_default_flags.load(), stream);
 }
 
 int savgol_apply_valid_batch_f32(const SavgolFilter *filter, const float *d_in, float *d_out, size_t channels,
                                  size_t length, size_t in_ld, size_t out_ld, void *stream)
 {
-    return enqueue_batch<float>("savgol_apply_valid_batch_f32", filter, d_in, d_out, channels, length, in_ld, out_ld,
-                                VALID, static_cast<hipStream_t>(stream), g_default_flags.load());
+    return savgol_apply_valid_batch_f32_ex(filter, d_in, d_out, channels, length, in_ld, out_ld, g_default_flags.load(), stream);
 }
 
 int savgol_apply_valid_batch_f64(const SavgolFilter *filter, const double *d_in, double *d_out, size_t channels,
                                  size_t length, size_t in_ld, size_t out_ld, void *stream)
 {
-    return enqueue_batch<double>("savgol_apply_valid_batch_f64", filter, d_in, d_out, channels, length, in_ld, out_ld,
-                                 VALID, static_cast<hipStream_t>(stream), g_default_flags.load());
+    return savgol_apply_valid_batch_f64_ex(filter, d_in, d_out, channels, length, in_ld, out_ld, g_default_flags.load(), stream);
 }
 
 int savgol_apply_strided_batch_f32(const SavgolFilter *filter, const void *d_in, size_t in_stride, size_t in_offset,
@@ -1091,6 +1072,7 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter, const void *d_
 {
     const char *who = "savgol_apply_strided_batch_f32";
     if (!flags_ok(who, flags)) return -1;
+    // (records have no row pitch to check, and the length refusal has this call's own wording)
     if (!filter || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
     if (!filter_sane(filter, who)) return -1;
     if (count < (size_t)filter->window_size) { sg_set_error("%s: count < window size", who); return -1; }
@@ -1119,10 +1101,10 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter, const void *d_
         } else disjoint = false;
     }
     if (!(flags & SAVGOL_BATCH_REFERENCE_SUMMATION) && aligned && disjoint && count <= LAUNCH_MAX_LENGTH) {
-        const int mode = (variant == FULL) ? (int)filter->config.boundary : (int)SAVGOL_BOUNDARY_POLYNOMIAL;
-        const bool poly = mode == SAVGOL_BOUNDARY_POLYNOMIAL;
-        const FilterPlan *plan = plan_get(ctx, filter, poly ? NEED_EDGES : 0u);
+        const CallShape shape = call_shape(filter, variant, count);
+        const FilterPlan *plan = plan_get(ctx, filter, shape.want_edges ? NEED_EDGES : 0u);
         if (!plan) return -1;
+        const OutputPart o = output_part(filter, shape, flags, false, false);
         sg::JobStrided job;
         memset(&job, 0, sizeof(job));
         job.in_pitch = (long long)in_channel_pitch; job.out_pitch = (long long)out_channel_pitch;
@@ -1131,26 +1113,17 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter, const void *d_
         const unsigned TW = 64u * (unsigned)sg::VPL_NARROW * 4u;
         job.tiles_per_channel = (unsigned)((count + TW - 1) / TW);
         sg::division_magic(job.tiles_per_channel, &job.tpc_magic, &job.tpc_shift);
-        job.dt_inv = dt_inverse(filter);
-        job.store_lo = poly ? (unsigned)n : 0u;
-        job.store_hi = poly ? (unsigned)(count - n) : (unsigned)count;
-        job.flags = ((unsigned)mode & sg::JOB_MODE_MASK);
-        if (mode < 0 || mode > 255) job.flags = 255u;
-        if (job.dt_inv != 1.0f) job.flags |= sg::JOB_SCALE;
-        if (poly) {                                                      // the edge rows ride in the same launch (sg1d_edge_item)
-            job.edges = plan->d_edges;
-            if ((flags & SAVGOL_BATCH_CORRECT_LEADING_EDGE) && (filter->config.derivative & 1)) job.flags |= sg::JOB_EDGE_NEGATE;
-        }
-        const size_t max_ch = (size_t)sg::MAX_TILES_PER_LAUNCH / ((size_t)job.tiles_per_channel + 2);
-        for (size_t c0 = 0; c0 < channels; c0 += max_ch) {
-            const size_t nc = (channels - c0 < max_ch) ? channels - c0 : max_ch;
-            job.in = reinterpret_cast<const char *>(ia) + c0 * in_channel_pitch;
-            job.out = reinterpret_cast<char *>(oa) + c0 * out_channel_pitch;
-            job.total_tiles = (unsigned)(nc * job.tiles_per_channel);
-            job.edge_items = poly ? (unsigned)(2 * nc) : 0u;
-            unsigned blocks = (job.total_tiles + job.edge_items + 3u) / 4u;
-            blocks = (blocks + 7u) & ~7u;
-            if (sg::launch_strided(n, job, plan->taps32, blocks, st) != 0) return -1;
+        job.dt_inv = o.dt_inv;
+        job.store_lo = shape.store_lo;
+        job.store_hi = shape.store_hi;
+        job.flags = shape.mode_flags | o.flags;
+        job.edges = shape.want_edges ? plan->d_edges : nullptr;             // the edge rows ride in the same launch (sg1d_edge_item)
+        for (ChannelGroups g{channels, launch_max_channels(job.tiles_per_channel, 2)}; g.next();) {
+            job.in = reinterpret_cast<const char *>(ia) + g.c0 * in_channel_pitch;
+            job.out = reinterpret_cast<char *>(oa) + g.c0 * out_channel_pitch;
+            job.total_tiles = (unsigned)(g.nc * job.tiles_per_channel);
+            job.edge_items = shape.want_edges ? (unsigned)(2 * g.nc) : 0u;
+            if (sg::launch_strided(n, job, plan->taps32, grid_blocks(job.total_tiles + job.edge_items), st) != 0) return -1;
         }
         return 0;
     }
@@ -1159,8 +1132,7 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter, const void *d_
     //      field into dense rows, filter, scatter back.  The two dense frames are this call's own, allocated and freed in stream
     //      order (sg::scratch_alloc: the library's own retained pool): no shared arena, no lock, no synchronise -- the call only enqueues. ----
     const size_t ld = (count + 3) & ~(size_t)3;
-    float *dense = nullptr;
-    dense = static_cast<float *>(sg::scratch_alloc(ctx, 2 * channels * ld * sizeof(float), st, "scratch (strided staging)"));
+    float *dense = static_cast<float *>(sg::scratch_alloc(ctx, 2 * channels * ld * sizeof(float), st, "scratch (strided staging)"));
     if (!dense) return -1;
     float *result = dense + channels * ld;
     int rc = 0;
@@ -1182,6 +1154,37 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter, const void *d_
 // reference-order kernel (sg1d_reference_order_kernel): the host link bounds them anyway, and a program that switches
 // from the reference library gets the reference's outputs bit for bit.
 // ------------------------------------------------------------------------------------------------
+// One host signal, FULL (`output` takes length samples) or VALID (length - 2n), by the cheapest route that serves it: small service ->
+// pipelined copies -> zero copy -> plain copies through the arena.  Caller holds ctx->mu.  0, or -1 with the error text set.
+static int host_call(const char *who, DeviceCtx *ctx, const SavgolFilter *f, const float *input, float *output, size_t length, Variant variant)
+{
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)f->config.half_window : length;
+    const int rc = small_host_call(who, ctx, f, input, output, length, variant);
+    if (rc <= 0) return rc;
+    // pipelined unless the two host buffers overlap in a way a chunked download would corrupt.  FULL in place is fine (a chunk is downloaded only
+    // after the samples it overwrites went up), a shifted overlap is not; VALID writes output[j - n], so even output == input is a shifted overlap.
+    // Those cases keep the upload-everything-first paths below.
+    const bool overlap = (uintptr_t)input < (uintptr_t)(output + out_len) && (uintptr_t)output < (uintptr_t)(input + length);
+    if (length >= PIPE_MIN_LENGTH && length <= ((size_t)1 << 30) && !(overlap && (variant == VALID || input != output)))
+        return host_apply_pipelined(who, ctx, f, input, output, length, variant);
+    const size_t ld = (length + 3) & ~(size_t)3;
+    if (zero_copy_length(length)) {
+        float *pin = static_cast<float *>(sg::ctx_pinned(ctx, 2 * ld * sizeof(float)));
+        if (!pin) return -1;
+        memcpy(pin, input, length * sizeof(float));
+        if (enqueue_batch<float>(who, f, pin, pin + ld, 1, length, ld, ld, variant, nullptr, host_call_flags()) != 0 || !sg::hip_ok(hipStreamSynchronize(nullptr), who)) return -1;
+        memcpy(output, pin + ld, out_len * sizeof(float));
+        return 0;
+    }
+    float *d_in = static_cast<float *>(sg::ctx_arena(ctx, 2 * ld * sizeof(float)));
+    if (!d_in) return -1;
+    float *d_out = d_in + ld;
+    const bool ok = sg::hip_ok(hipMemcpyAsync(d_in, input, length * sizeof(float), hipMemcpyHostToDevice, nullptr), "H2D copy") &&
+                    enqueue_batch<float>(who, f, d_in, d_out, 1, length, ld, ld, variant, nullptr, host_call_flags()) == 0 &&
+                    sg::hip_ok(hipMemcpy(output, d_out, out_len * sizeof(float), hipMemcpyDeviceToHost), "D2H copy");
+    return ok ? 0 : -1;
+}
+
 int savgol_apply(const SavgolFilter *filter, const float *input, float *output, size_t length)
 {
     if (!filter || !input || !output) {
@@ -1193,39 +1196,12 @@ int savgol_apply(const SavgolFilter *filter, const float *input, float *output, 
         return -1;
     }
     DeviceCtx *ctx = sg::ctx_get();
-    if (!ctx) { fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error()); return -1; }
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    {
-        const int rc = small_host_call("savgol_apply", ctx, filter, input, output, length, FULL);
-        if (rc == 0) return 0;
-        if (rc < 0) { fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error()); return -1; }
+    if (ctx) {
+        std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+        if (host_call("savgol_apply", ctx, filter, input, output, length, FULL) == 0) return 0;
     }
-    // pipelined unless the two host buffers overlap without being the same (in place is fine: a chunk is downloaded only
-    // after the samples it overwrites went up; a shifted overlap is not, so that case keeps the upload-everything-first path)
-    const bool partial_overlap = input != output && (uintptr_t)input < (uintptr_t)(output + length) && (uintptr_t)output < (uintptr_t)(input + length);
-    if (length >= PIPE_MIN_LENGTH && length <= ((size_t)1 << 30) && !partial_overlap) {
-        if (host_apply_pipelined("savgol_apply", ctx, filter, input, output, length, FULL) == 0) return 0;
-        fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error());
-        return -1;
-    }
-    const size_t ld = (length + 3) & ~(size_t)3;
-    if (zero_copy_length(length)) {
-        float *pin = static_cast<float *>(sg::ctx_pinned(ctx, 2 * ld * sizeof(float)));
-        if (!pin) { fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error()); return -1; }
-        memcpy(pin, input, length * sizeof(float));
-        if (enqueue_batch<float>("savgol_apply", filter, pin, pin + ld, 1, length, ld, ld, FULL, nullptr, host_call_flags()) != 0 ||
-            !sg::hip_ok(hipStreamSynchronize(nullptr), "savgol_apply")) { fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error()); return -1; }
-        memcpy(output, pin + ld, length * sizeof(float));
-        return 0;
-    }
-    float *d_in = static_cast<float *>(sg::ctx_arena(ctx, 2 * ld * sizeof(float)));
-    if (!d_in) { fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error()); return -1; }
-    float *d_out = d_in + ld;
-    bool ok = sg::hip_ok(hipMemcpyAsync(d_in, input, length * sizeof(float), hipMemcpyHostToDevice, nullptr), "H2D copy");
-    ok = ok && enqueue_batch<float>("savgol_apply", filter, d_in, d_out, 1, length, ld, ld, FULL, nullptr, host_call_flags()) == 0;
-    ok = ok && sg::hip_ok(hipMemcpy(output, d_out, length * sizeof(float), hipMemcpyDeviceToHost), "D2H copy");
-    if (!ok) { fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error()); return -1; }
-    return 0;
+    fprintf(stderr, "savgol_apply: %s\n", savgol_hip_last_error());
+    return -1;
 }
 
 size_t savgol_apply_valid(const SavgolFilter *filter, const float *input, size_t input_length, float *output)
@@ -1233,81 +1209,46 @@ size_t savgol_apply_valid(const SavgolFilter *filter, const float *input, size_t
     if (!filter || !input || !output) return 0;
     if (input_length < (size_t)filter->window_size) return 0;
     DeviceCtx *ctx = sg::ctx_get();
-    if (!ctx) { fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error()); return 0; }
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    const size_t out_len = input_length - 2 * (size_t)filter->config.half_window;
-    {
-        const int rc = small_host_call("savgol_apply_valid", ctx, filter, input, output, input_length, VALID);
-        if (rc == 0) return out_len;
-        if (rc < 0) { fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error()); return 0; }
+    if (ctx) {
+        std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+        if (host_call("savgol_apply_valid", ctx, filter, input, output, input_length, VALID) == 0) return input_length - 2 * (size_t)filter->config.half_window;
     }
-    // VALID writes output[j - n]: even output == input is a shifted overlap, so only disjoint buffers are pipelined
-    const bool overlap = (uintptr_t)input < (uintptr_t)(output + out_len) && (uintptr_t)output < (uintptr_t)(input + input_length);
-    if (input_length >= PIPE_MIN_LENGTH && input_length <= ((size_t)1 << 30) && !overlap) {
-        if (host_apply_pipelined("savgol_apply_valid", ctx, filter, input, output, input_length, VALID) == 0) return out_len;
-        fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error());
-        return 0;
-    }
-    const size_t ld = (input_length + 3) & ~(size_t)3;
-    if (zero_copy_length(input_length)) {
-        float *pin = static_cast<float *>(sg::ctx_pinned(ctx, 2 * ld * sizeof(float)));
-        if (!pin) { fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error()); return 0; }
-        memcpy(pin, input, input_length * sizeof(float));
-        if (enqueue_batch<float>("savgol_apply_valid", filter, pin, pin + ld, 1, input_length, ld, ld, VALID, nullptr, host_call_flags()) != 0 ||
-            !sg::hip_ok(hipStreamSynchronize(nullptr), "savgol_apply_valid")) { fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error()); return 0; }
-        memcpy(output, pin + ld, out_len * sizeof(float));
-        return out_len;
-    }
-    float *d_in = static_cast<float *>(sg::ctx_arena(ctx, 2 * ld * sizeof(float)));
-    if (!d_in) { fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error()); return 0; }
-    float *d_out = d_in + ld;
-    bool ok = sg::hip_ok(hipMemcpyAsync(d_in, input, input_length * sizeof(float), hipMemcpyHostToDevice, nullptr), "H2D copy");
-    ok = ok && enqueue_batch<float>("savgol_apply_valid", filter, d_in, d_out, 1, input_length, ld, ld, VALID, nullptr, host_call_flags()) == 0;
-    ok = ok && sg::hip_ok(hipMemcpy(output, d_out, out_len * sizeof(float), hipMemcpyDeviceToHost), "D2H copy");
-    if (!ok) { fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error()); return 0; }
-    return out_len;
+    fprintf(stderr, "savgol_apply_valid: %s\n", savgol_hip_last_error());
+    return 0;
 }
 
+// The float fields are picked on the host (pure data movement), the arithmetic runs on the GPU.  Its ladder is host_call's without the pipelined
+// step, on buffers it already holds: the gathered field lies in the pinned staging buffer, so the zero-copy step runs on it as it is.
 int savgol_apply_strided(const SavgolFilter *filter, const void *input, size_t in_stride, size_t in_offset, void *output,
                          size_t out_stride, size_t out_offset, size_t count)
 {
+    const char *who = "savgol_apply_strided";
     if (!filter || !input || !output) return -1;
     if (count < (size_t)filter->window_size) return -1;
     DeviceCtx *ctx = sg::ctx_get();
-    if (!ctx) { fprintf(stderr, "savgol_apply_strided: %s\n", savgol_hip_last_error()); return -1; }
+    if (!ctx) { fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    // the float fields are picked on the host (pure data movement), the arithmetic runs on the GPU
     const size_t ld = (count + 3) & ~(size_t)3;
     float *stage = static_cast<float *>(sg::ctx_pinned(ctx, 2 * ld * sizeof(float)));      // gathered field, then (short signals) the result
     float *d_in = static_cast<float *>(sg::ctx_arena(ctx, 2 * ld * sizeof(float)));
-    if (!stage || !d_in) { fprintf(stderr, "savgol_apply_strided: %s\n", savgol_hip_last_error()); return -1; }
-    float *d_out = d_in + ld;
+    if (!stage || !d_in) { fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
     const char *ib = static_cast<const char *>(input) + in_offset;
     for (size_t i = 0; i < count; ++i) memcpy(&stage[i], ib + i * in_stride, sizeof(float));
-    {
-        const int rc = small_host_call("savgol_apply_strided", ctx, filter, stage, stage + ld, count, (host_call_flags() & SAVGOL_BATCH_BOUNDARY_AWARE) ? FULL : FULL_POLY_EDGES);
-        if (rc < 0) { fprintf(stderr, "savgol_apply_strided: %s\n", savgol_hip_last_error()); return -1; }
-        if (rc == 0) {
-            char *ob0 = static_cast<char *>(output) + out_offset;
-            for (size_t i = 0; i < count; ++i) memcpy(ob0 + i * out_stride, &stage[ld + i], sizeof(float));
-            return 0;
-        }
+    const unsigned flags = host_call_flags();
+    const Variant variant = (flags & SAVGOL_BATCH_BOUNDARY_AWARE) ? FULL : FULL_POLY_EDGES;
+    const float *result = stage + ld;
+    int rc = small_host_call(who, ctx, filter, stage, stage + ld, count, variant);
+    if (rc > 0 && zero_copy_length(count)) {
+        rc = (enqueue_batch<float>(who, filter, stage, stage + ld, 1, count, ld, ld, variant, nullptr, flags) == 0 && sg::hip_ok(hipStreamSynchronize(nullptr), who)) ? 0 : -1;
+    } else if (rc > 0) {
+        result = stage;
+        rc = (sg::hip_ok(hipMemcpy(d_in, stage, count * sizeof(float), hipMemcpyHostToDevice), "H2D copy") &&
+              enqueue_batch<float>(who, filter, d_in, d_in + ld, 1, count, ld, ld, variant, nullptr, flags) == 0 &&
+              sg::hip_ok(hipMemcpy(stage, d_in + ld, count * sizeof(float), hipMemcpyDeviceToHost), "D2H copy")) ? 0 : -1;
     }
-    if (zero_copy_length(count)) {                               // short signals: the kernel works on the pinned staging buffer itself
-        float *pin = stage;
-        if (enqueue_batch<float>("savgol_apply_strided", filter, pin, pin + ld, 1, count, ld, ld, (host_call_flags() & SAVGOL_BATCH_BOUNDARY_AWARE) ? FULL : FULL_POLY_EDGES,
-                                 nullptr, host_call_flags()) != 0 ||
-            !sg::hip_ok(hipStreamSynchronize(nullptr), "savgol_apply_strided")) { fprintf(stderr, "savgol_apply_strided: %s\n", savgol_hip_last_error()); return -1; }
-        char *ob2 = static_cast<char *>(output) + out_offset;
-        for (size_t i = 0; i < count; ++i) memcpy(ob2 + i * out_stride, &pin[ld + i], sizeof(float));
-        return 0;
-    }
-    bool ok = sg::hip_ok(hipMemcpy(d_in, stage, count * sizeof(float), hipMemcpyHostToDevice), "H2D copy");
-    ok = ok && enqueue_batch<float>("savgol_apply_strided", filter, d_in, d_out, 1, count, ld, ld, (host_call_flags() & SAVGOL_BATCH_BOUNDARY_AWARE) ? FULL : FULL_POLY_EDGES, nullptr, host_call_flags()) == 0;
-    ok = ok && sg::hip_ok(hipMemcpy(stage, d_out, count * sizeof(float), hipMemcpyDeviceToHost), "D2H copy");
-    if (!ok) { fprintf(stderr, "savgol_apply_strided: %s\n", savgol_hip_last_error()); return -1; }
+    if (rc < 0) { fprintf(stderr, "%s: %s\n", who, savgol_hip_last_error()); return -1; }
     char *ob = static_cast<char *>(output) + out_offset;
-    for (size_t i = 0; i < count; ++i) memcpy(ob + i * out_stride, &stage[i], sizeof(float));
+    for (size_t i = 0; i < count; ++i) memcpy(ob + i * out_stride, &result[i], sizeof(float));
     return 0;
 }
 
