@@ -87,8 +87,9 @@ __device__ __forceinline__ int remap_index(int i, int L, int mode, bool &zero)
     return i;
 }
 
-template <typename T, int N, int V = vectors_per_lane(sizeof(T), N)>
+template <typename T_, int N, int V = vectors_per_lane(sizeof(T_), N)>
 struct K1D {
+    typedef T_ T;
     typedef typename V16<T>::type VT;
     static constexpr int E    = V16<T>::E;
     static constexpr int VPL  = V;                           // 16-B vectors of output per lane (sg_k1d_host.hpp: narrow / wide tiles)
@@ -335,6 +336,12 @@ __device__ __forceinline__ void sg1d_edge_item(const JobStrided &job, unsigned i
                              [&](long long i, float v) { *reinterpret_cast<float *>(orow + i * job.out_stride) = v; });
 }
 
+// ---------------------------------------------------------------------------------------------
+// The pieces of the tile algorithm that every tile kernel shares -- sg1d_tile_body below, sg1d_multi_body (sg_k1d_multi.hpp) and
+// sg1d_h16_body (sg_k1d_h16.hpp) are these in calls, each with its own inner product between them.  The fused and the 16-bit calls promise
+// the bits of the fp32 single call: one definition of each staging / centring / finishing rule is what keeps that promise on the device.
+// ---------------------------------------------------------------------------------------------
+
 // Work distribution: ONE TILE PER WAVE, blocks dispatched in order (grid = total_tiles / 4).  Round 1 ran a persistent
 // grid (resident waves striding over the tiles, next tile prefetched into registers); measured on MI355X that shape caps a
 // read+write stream at 5.2-5.5 TB/s, while the same tiles handed out by the hardware dispatcher in block order stream at
@@ -343,6 +350,228 @@ __device__ __forceinline__ void sg1d_edge_item(const JobStrided &job, unsigned i
 // round-robin placement) get neighbouring tiles -- each XCD sweeps its own eighth of the batch -- so the halo a tile shares
 // with its neighbour is an L2 hit; placement affects speed only.  Channel-end tiles (slower, see below) are simply tiles
 // that take longer; the dispatcher balances them.
+// Returns the tile of wave `wave` of this block (WAVES waves per block); tiles >= job.total_tiles are the edge items.
+template <int WAVES>
+__device__ __forceinline__ unsigned sg1d_tile_of_wave(const Job1D &job, int wave)
+{
+    const unsigned nb8 = gridDim.x >> 3;
+    unsigned blk = blockIdx.x;
+    if (blk < nb8 * 8u) {
+        // (the host counts chunks in blocks of four tiles: a kernel family built with fewer waves per block has proportionally more blocks per chunk)
+        const unsigned cs = job.xcd_chunk_log2 == 0 || job.xcd_chunk_log2 >= 32u ? job.xcd_chunk_log2 : job.xcd_chunk_log2 + (WAVES == 4 ? 0u : WAVES == 2 ? 1u : 2u);
+        if (cs == 0) blk = (blk & 7u) * nb8 + (blk >> 3);
+        else if (cs < 32u) {
+            const unsigned span = 8u << cs, q = blk >> (cs + 3u);
+            if ((q + 1u) * span <= nb8 * 8u) { const unsigned r = blk & (span - 1u); blk = (((q << 3) + (r & 7u)) << cs) + (r >> 3); }   // the last, partial span keeps launch order
+        }
+    }
+    return blk * WAVES + wave;
+}
+
+// tile / tiles_per_channel, on the scalar unit (Job1D or JobStrided)
+template <typename Job>
+__device__ __forceinline__ unsigned tile_channel(const Job &job, unsigned tile)
+{
+    return job.tpc_shift >= 32 ? tile : (__umulhi(tile, job.tpc_magic) >> job.tpc_shift);
+}
+
+// slab vector lane + 64 s, the row-wise view of a slab (staging writes, centring, the padded result rows): when VPL divides 64 the pad count
+// splits, (lane + 64 s)/VPL = lane/VPL + s*64/VPL, so one VGPR holds the lane part and s goes into the instruction's immediate offset
+template <typename K>
+struct SlabRows {
+    char *slab, *slab_row;
+    int lane;
+    __device__ __forceinline__ SlabRows(char *slab_, int lane_) : slab(slab_), slab_row(slab_ + slab_vec_off<K::VPL>(lane_)), lane(lane_) {}
+    __device__ __forceinline__ typename K::VT *operator()(int s) const
+    {
+        if constexpr (64 % K::VPL == 0) return reinterpret_cast<typename K::VT *>(slab_row + s * (16 * (64 + 64 / K::VPL)));
+        else return reinterpret_cast<typename K::VT *>(slab + slab_vec_off<K::VPL>(lane + 64 * s));
+    }
+};
+
+// How rows are stored in memory, for the first and the last hop of a tile: the element type, the raw vector that carries one slab vector's
+// E samples, and the steps between them and the slab's T / VT.  Rows of the slab's own type (fp32, fp64) move as they are; sg_k1d_h16.hpp has
+// the 16-bit storage types.
+template <typename T>
+struct SameStorage {
+    typedef T Elem;
+    typedef typename V16<T>::type VT;
+    typedef VT Raw;
+    static __device__ __forceinline__ Raw ld_stream(const Raw *p) { return sg::ld_stream(p); }
+    static __device__ __forceinline__ void st_stream(Raw *p, const VT &v) { sg::st_stream(p, v); }
+    static __device__ __forceinline__ VT widen(const Raw &r) { return r; }
+    static __device__ __forceinline__ T widen1(T x) { return x; }
+    static __device__ __forceinline__ Raw narrow(const VT &v) { return v; }
+    static __device__ __forceinline__ T narrow1(T x) { return x; }
+};
+
+// ---- stage tile + halo of an out-of-place call into the slab (slab vector v <-> samples ts - NA + v E .. of `row`) ----
+template <typename K, typename S>
+__device__ __forceinline__ void stage_tile(const SlabRows<K> &row_vec, const typename S::Elem *row, int ts, int L, unsigned flags, int lane)
+{
+    typedef typename K::VT VT;
+    typedef typename S::Raw Raw;
+    constexpr int E = K::E, TW = K::TW, NA = K::NA, HV = K::HV, VPL = K::VPL, TV = K::TV;
+    char *const slab = row_vec.slab;
+    // a tile is "full" when every vector of tile + halo lies inside the row: the common case
+    if ((flags & JOB_VEC_IN) && ts - NA >= 0 && ts + TW + NA <= L) {
+        const Raw *src = reinterpret_cast<const Raw *>(row + (ts - NA));
+        Raw p[VPL + 1];                                                   // every load is issued before the first conversion or LDS write
+#pragma unroll
+        for (int s = 0; s < VPL; ++s) p[s] = S::ld_stream(src + lane + 64 * s);
+        if (lane < 2 * HV) p[VPL] = src[TV + lane];                       // halo: re-read by the neighbour tile, keep it cached
+#pragma unroll
+        for (int s = 0; s < VPL; ++s) *row_vec(s) = S::widen(p[s]);
+        if (lane < 2 * HV) *row_vec(VPL) = S::widen(p[VPL]);
+    } else {
+        // Channel ends, short rows, rows without vector alignment.  Vectors that lie wholly inside the
+        // row are still moved as vectors; the rest (the part of the halo that sticks out of the row,
+        // remapped per boundary mode; everything if the row is unaligned) goes element by element.
+        const bool vec = (flags & JOB_VEC_IN) != 0;
+        const int mode = (int)(flags & JOB_MODE_MASK);
+        const int lim = L + NA;                                      // nothing beyond is ever used
+#pragma unroll
+        for (int s = 0; s < VPL + 1; ++s) {
+            const int v = lane + 64 * s;
+            const int g0 = ts - NA + v * E;
+            if (v < K::SV && vec && g0 >= 0 && g0 + E <= L)
+                *reinterpret_cast<VT *>(slab + slab_vec_off<VPL>(v)) = S::widen(*reinterpret_cast<const Raw *>(row + g0));
+        }
+#pragma unroll 4
+        for (int e = lane; e < K::SL; e += 64) {
+            int g = ts - NA + e;
+            const int g0 = g - (e % E);
+            const bool direct = vec && g0 >= 0 && g0 + E <= L;
+            if (!direct) {
+                // beyond L + NA nothing a STORED output needs is read -- but the slab is whatever the previous block left there, and round 5's
+                // x-stationary inner product multiplies the sample one past a window by a zero tap (0 x NaN): zero-fill instead of skipping
+                typename K::T x = 0;
+                if (g < lim) {
+                    bool zero = false;
+                    if (g < 0 || g >= L) g = remap_index(g, L, mode, zero);
+                    if (!zero) x = S::widen1(row[g]);
+                }
+                *reinterpret_cast<typename K::T *>(slab + slab_vec_off<VPL>(e / E) + (e % E) * (int)sizeof(typename K::T)) = x;
+            }
+        }
+    }
+}
+
+// ---- derivative filters (JOB_CENTRE, fp32): centre the tile.  sum_k w_k x_k = sum_k w_k (x_k - c) + c sum_k w_k for any c; with c = the mean of the
+// tile's body the partial sums / block moments meet the signal's variation across the tile instead of its offset.  A filter whose
+// weights sum to ~0 on a signal riding on a large offset stood at 1.1-1.4 x the reference's own error (block moments from half window 20: the
+// blocks' shares cancel only after each has been rounded at the offset's size; tools/offset_probe_1d.py, R6.16).  Smoothing filters do not
+// come here (the flag is off: nothing of this runs).  Subtracts c from the whole slab and returns it; the caller syncs before the next window read.
+template <typename K>
+__device__ __forceinline__ typename K::T centre_slab(const SlabRows<K> &row_vec, int lane)
+{
+    typedef typename K::T T;
+    typedef typename K::VT VT;
+    constexpr int E = K::E, TW = K::TW, HV = K::HV, VPL = K::VPL, TV = K::TV;
+    // c = the MEAN of the tile's body (a single sample of a zero-mean signal would double what the sums meet): every lane's partial sum, then an
+    // xor butterfly -- both partners of a step add the same two numbers, so all 64 lanes end with the same bits
+    VT p[VPL + 1];
+    T part = T(0);
+#pragma unroll
+    for (int s = 0; s < VPL + 1; ++s) {
+        if (s < VPL || lane < 2 * HV) {
+            p[s] = *row_vec(s);
+            // slab vectors HV .. HV + TV - 1 are the body: vector index lane + 64 s
+            const int v = lane + 64 * s;
+            if (v >= HV && v < HV + TV) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) part += vget(p[s], e);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    T centre = part * (T(1) / T(TW));
+    if (!(centre - centre == T(0))) centre = T(0);     // Inf / NaN in the tile: leave it as it is
+#pragma unroll
+    for (int s = 0; s < VPL + 1; ++s) {
+        if (s < VPL || lane < 2 * HV) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) vset(p[s], e, vget(p[s], e) - centre);
+            *row_vec(s) = p[s];
+        }
+    }
+    return centre;
+}
+
+// ---- after the inner product: the centre added back (JOB_CENTRE), the derivative's 1 / dt^d (JOB_SCALE) ----
+template <typename T, int R>
+__device__ __forceinline__ void finish_acc(T (&acc)[R], unsigned flags, T centre, T centre_sum, T dt_inv)
+{
+    if (flags & JOB_CENTRE) {
+        const T back = centre * centre_sum;
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] += back;
+    }
+    if (flags & JOB_SCALE) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] *= dt_inv;
+    }
+}
+
+// ---- results into LDS at `base` (the slab once its window reads are done, or a region of their own): lane's R outputs as VPL vectors.
+// 8 vectors per lane take the swizzled layout (result_vec_off8); other tile widths keep the slab's padded one ----
+template <typename K>
+__device__ __forceinline__ void put_results(char *base, int lane, const typename K::T (&acc)[K::R])
+{
+    typedef typename K::VT VT;
+    constexpr int E = K::E, VPL = K::VPL;
+    constexpr bool SWZ = (VPL == 8);
+    // lane's vector s: byte 128 lane + 16 (s ^ lane % 8) = (128 lane + 16 (lane % 8)) ^ (16 s): one v_xor_b32 with a literal per write
+    const int wbase = SWZ ? 128 * lane + 16 * (lane & 7) : 16 * (lane * (VPL + 1));
+#pragma unroll
+    for (int s = 0; s < VPL; ++s) {
+        VT o;
+#pragma unroll
+        for (int e = 0; e < E; ++e) vset(o, e, acc[s * E + e]);
+        *reinterpret_cast<VT *>(base + (SWZ ? (wbase ^ (16 * s)) : wbase + 16 * s)) = o;
+    }
+}
+
+// ---- ... and out of it as coalesced rows to HBM, in the storage S of the output rows: outputs [lo, hi) of the channel are stored ----
+template <typename K, typename S>
+__device__ __forceinline__ void store_tile(char *base, typename S::Elem *orow, int ts, int lo, int hi, unsigned flags, int lane)
+{
+    typedef typename K::VT VT;
+    typedef typename S::Raw Raw;
+    constexpr int E = K::E, TW = K::TW, VPL = K::VPL;
+    constexpr bool SWZ = (VPL == 8);
+    if ((flags & JOB_VEC_OUT) && ts >= lo && ts + TW <= hi) {
+        // vector lane + 64 s of the tile: with the swizzle its offset splits into a lane part (one VGPR) and 1024 s (an immediate)
+        const char *const rbase = base + (SWZ ? result_vec_off8(lane) : 0);
+        const SlabRows<K> row_vec(base, lane);
+        Raw *dst = reinterpret_cast<Raw *>(orow + ts) + lane;
+#pragma unroll
+        for (int s = 0; s < VPL; ++s) {
+            const VT o = SWZ ? *reinterpret_cast<const VT *>(rbase + 1024 * s) : *row_vec(s);
+            S::st_stream(dst + 64 * s, o);
+        }
+    } else {
+        // first / last tile of a channel (the stored range ends inside it) or unaligned output rows
+        const bool vec = (flags & JOB_VEC_OUT) != 0;
+#pragma unroll
+        for (int s = 0; s < VPL; ++s) {
+            const int p = lane + 64 * s;
+            const int g0 = ts + p * E;
+            const VT o = *reinterpret_cast<const VT *>(base + (SWZ ? result_vec_off8(p) : slab_vec_off<VPL>(p)));
+            if (vec && g0 >= lo && g0 + E <= hi) {
+                *reinterpret_cast<Raw *>(orow + g0) = S::narrow(o);
+            } else {
+#pragma unroll
+                for (int e = 0; e < E; ++e)
+                    if (g0 + e >= lo && g0 + e < hi) orow[g0 + e] = S::narrow1(vget(o, e));
+            }
+        }
+    }
+}
+
+// The single-output tile kernel's body.  CV is the convolution policy (DirectConv below, the block-moment policies of sg_k1d_momenth.hpp /
+// sg_k1d_moment64.hpp); in-place calls (Job1D::phase) are this body's alone.
 template <typename T, int N, typename CV>
 __device__ __forceinline__ void sg1d_tile_body(const Job1D &job, const typename CV::Args &taps)
 {
@@ -355,18 +584,7 @@ __device__ __forceinline__ void sg1d_tile_body(const Job1D &job, const typename 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform, lives in an SGPR
     char *slab = smem + wave * K::SLAB;
 
-    const unsigned nb8 = gridDim.x >> 3;
-    unsigned blk = blockIdx.x;
-    if (blk < nb8 * 8u) {
-        // (the host counts chunks in blocks of four tiles: a kernel family built with fewer waves per block has proportionally more blocks per chunk)
-        const unsigned cs = job.xcd_chunk_log2 == 0 || job.xcd_chunk_log2 >= 32u ? job.xcd_chunk_log2 : job.xcd_chunk_log2 + (K::WAVES == 4 ? 0u : K::WAVES == 2 ? 1u : 2u);
-        if (cs == 0) blk = (blk & 7u) * nb8 + (blk >> 3);
-        else if (cs < 32u) {
-            const unsigned span = 8u << cs, q = blk >> (cs + 3u);
-            if ((q + 1u) * span <= nb8 * 8u) { const unsigned r = blk & (span - 1u); blk = (((q << 3) + (r & 7u)) << cs) + (r >> 3); }   // the last, partial span keeps launch order
-        }
-    }
-    const unsigned tile = blk * K::WAVES + wave;
+    const unsigned tile = sg1d_tile_of_wave<K::WAVES>(job, wave);
     if (tile >= job.total_tiles) {                                        // wave-uniform: past the tiles come the edge items, if any
         if (tile - job.total_tiles < job.edge_items) sg1d_edge_item<T, N>(job, tile - job.total_tiles, lane);
         return;
@@ -375,14 +593,13 @@ __device__ __forceinline__ void sg1d_tile_body(const Job1D &job, const typename 
     const T *__restrict__ gin  = static_cast<const T *>(job.in);
     T *__restrict__       gout = static_cast<T *>(job.out);
     const int L = (int)job.length;
-    const int mode = (int)(job.flags & JOB_MODE_MASK);
 
 #ifdef SG_STAMPS
     const bool stamp_on = (blockIdx.x == 8 && wave == 1);
     const int stamp_it = 0;
 #endif
     SG_STAMP(0);
-    const unsigned c = job.tpc_shift >= 32 ? tile : (__umulhi(tile, job.tpc_magic) >> job.tpc_shift);   // tile / tiles_per_channel, on the scalar unit
+    const unsigned c = tile_channel(job, tile);
     // in-place colour phases (Job1D::phase): the launch holds the even (1) or the odd (2) tiles of every channel.  Stash layout (Job1D): one slot of
     // [left NA | right NA] per ODD tile (slot of tile k = c * (T / 2) + (k - 1) / 2), and per channel `ends` = [tile 0's left | the last tile's right |
     // tile T-2's right when the last tile is shorter than NA | pad], NA samples each
@@ -408,13 +625,7 @@ __device__ __forceinline__ void sg1d_tile_body(const Job1D &job, const typename 
     }
     const int ts = (int)k * TW;
     const T *__restrict__ row = gin + (long long)c * job.in_ld;
-    // slab byte offset of vector lane + 64*s: when VPL divides 64 the pad count splits, (lane + 64 s)/VPL = lane/VPL + s*64/VPL,
-    // so one VGPR holds the lane part and s goes into the instruction's immediate offset
-    char *const slab_row = slab + slab_vec_off<VPL>(lane);
-    auto row_vec = [&](int s) -> VT * {
-        if constexpr (64 % VPL == 0) return reinterpret_cast<VT *>(slab_row + s * (16 * (64 + 64 / VPL)));
-        else return reinterpret_cast<VT *>(slab + slab_vec_off<VPL>(lane + 64 * s));
-    };
+    const SlabRows<K> row_vec(slab, lane);
 
     // ---- stage tile + halo into the slab ----
     if (st_left || st_right) {
@@ -447,48 +658,7 @@ __device__ __forceinline__ void sg1d_tile_body(const Job1D &job, const typename 
                 *reinterpret_cast<T *>(slab + slab_vec_off<VPL>(e / E) + (e % E) * (int)sizeof(T)) = x;
             }
         }
-    } else
-    // a tile is "full" when every 16-B vector of tile + halo lies inside the row: the common case
-    if ((job.flags & JOB_VEC_IN) && ts - NA >= 0 && ts + TW + NA <= L) {
-        const VT *src = reinterpret_cast<const VT *>(row + (ts - NA));
-        VT p[VPL + 1];
-#pragma unroll
-        for (int s = 0; s < VPL; ++s) p[s] = ld_stream(src + lane + 64 * s);
-        if (lane < 2 * HV) p[VPL] = src[TV + lane];                       // halo: re-read by the neighbour tile, keep it cached
-#pragma unroll
-        for (int s = 0; s < VPL; ++s) *row_vec(s) = p[s];
-        if (lane < 2 * HV) *row_vec(VPL) = p[VPL];
-    } else {
-        // Channel ends, short rows, rows without 16-B alignment.  Vectors that lie wholly inside the
-        // row are still moved as vectors; the rest (the part of the halo that sticks out of the row,
-        // remapped per boundary mode; everything if the row is unaligned) goes element by element.
-        const bool vec = (job.flags & JOB_VEC_IN) != 0;
-        const int lim = L + NA;                                      // nothing beyond is ever used
-#pragma unroll
-        for (int s = 0; s < VPL + 1; ++s) {
-            const int v = lane + 64 * s;
-            const int g0 = ts - NA + v * E;
-            if (v < K::SV && vec && g0 >= 0 && g0 + E <= L)
-                *reinterpret_cast<VT *>(slab + slab_vec_off<VPL>(v)) = *reinterpret_cast<const VT *>(row + g0);
-        }
-#pragma unroll 4
-        for (int e = lane; e < K::SL; e += 64) {
-            int g = ts - NA + e;
-            const int g0 = g - (e % E);
-            const bool direct = vec && g0 >= 0 && g0 + E <= L;
-            if (!direct) {
-                // beyond L + NA nothing a STORED output needs is read -- but the slab is whatever the previous block left there, and round 5's
-                // x-stationary inner product multiplies the sample one past a window by a zero tap (0 x NaN): zero-fill instead of skipping
-                T x = T(0);
-                if (g < lim) {
-                    bool zero = false;
-                    if (g < 0 || g >= L) g = remap_index(g, L, mode, zero);
-                    if (!zero) x = row[g];
-                }
-                *reinterpret_cast<T *>(slab + slab_vec_off<VPL>(e / E) + (e % E) * (int)sizeof(T)) = x;
-            }
-        }
-    }
+    } else stage_tile<K, SameStorage<T>>(row_vec, row, ts, L, job.flags, lane);
     SG_STAMP(1);
     wave_lds_sync();
     SG_STAMP(2);
@@ -504,102 +674,25 @@ __device__ __forceinline__ void sg1d_tile_body(const Job1D &job, const typename 
         }
     }
 
-    // ---- derivative filters (JOB_CENTRE, fp32): centre the tile.  sum_k w_k x_k = sum_k w_k (x_k - c) + c sum_k w_k for any c; with c = the mean of the
-    // tile's body the partial sums / block moments below meet the signal's variation across the tile instead of its offset.  A filter whose
-    // weights sum to ~0 on a signal riding on a large offset stood at 1.1-1.4 x the reference's own error (block moments from half window 20: the
-    // blocks' shares cancel only after each has been rounded at the offset's size; tools/offset_probe_1d.py, R6.16).  Smoothing filters do not
-    // come here (the flag is off: nothing of this runs).  After the in-place slots have been written -- those must hold the raw samples.
+    // ---- derivative filters (JOB_CENTRE): centre the tile -- after the in-place slots have been written, those must hold the raw samples ----
     T centre = T(0);
     if (job.flags & JOB_CENTRE) {                          // uniform
-        // c = the MEAN of the tile's body (a single sample of a zero-mean signal would double what the sums meet): every lane's partial sum, then an
-        // xor butterfly -- both partners of a step add the same two numbers, so all 64 lanes end with the same bits
-        VT p[VPL + 1];
-        T part = T(0);
-#pragma unroll
-        for (int s = 0; s < VPL + 1; ++s) {
-            if (s < VPL || lane < 2 * HV) {
-                p[s] = *row_vec(s);
-                // slab vectors HV .. HV + TV - 1 are the body: vector index lane + 64 s
-                const int v = lane + 64 * s;
-                if (v >= HV && v < HV + TV) {
-#pragma unroll
-                    for (int e = 0; e < E; ++e) part += vget(p[s], e);
-                }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-        centre = part * (T(1) / T(TW));
-        if (!(centre - centre == T(0))) centre = T(0);     // Inf / NaN in the tile: leave it as it is
-#pragma unroll
-        for (int s = 0; s < VPL + 1; ++s) {
-            if (s < VPL || lane < 2 * HV) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) vset(p[s], e, vget(p[s], e) - centre);
-                *row_vec(s) = p[s];
-            }
-        }
+        centre = centre_slab(row_vec, lane);
         wave_lds_sync();
     }
 
     // ---- the convolution: lane owns outputs [lane*R, lane*R + R) of the tile ----
     T acc[R];
     CV::run(slab + 16 * (lane * (VPL + 1)), taps, acc, job.flags);
-    if (job.flags & JOB_CENTRE) {
-        const T back = centre * (T)job.centre_sum;
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] += back;
-    }
-    if (job.flags & JOB_SCALE) {
-        const T s = (T)job.dt_inv;
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] *= s;
-    }
+    finish_acc(acc, job.flags, centre, (T)job.centre_sum, (T)job.dt_inv);
     wave_lds_sync();                                   // all window reads done before overwrite
     SG_STAMP(3);
 
     // ---- results back through the slab, then coalesced rows to HBM ----
-    constexpr bool SWZ = (VPL == 8);                     // the swizzled result layout (result_vec_off8); other tile widths keep the padded one
-    {
-        // lane's vector s: byte 128 lane + 16 (s ^ lane % 8) = (128 lane + 16 (lane % 8)) ^ (16 s): one v_xor_b32 with a literal per write
-        const int wbase = SWZ ? 128 * lane + 16 * (lane & 7) : 16 * (lane * (VPL + 1));
-#pragma unroll
-        for (int s = 0; s < VPL; ++s) {
-            VT o;
-#pragma unroll
-            for (int e = 0; e < E; ++e) vset(o, e, acc[s * E + e]);
-            *reinterpret_cast<VT *>(slab + (SWZ ? (wbase ^ (16 * s)) : wbase + 16 * s)) = o;
-        }
-    }
+    put_results<K>(slab, lane, acc);
     wave_lds_sync();
     T *__restrict__ orow = gout + (long long)c * job.out_ld - (long long)job.out_shift;
-    const int lo = (int)job.store_lo, hi = (int)job.store_hi;
-    const bool whole = (job.flags & JOB_VEC_OUT) && ts >= lo && ts + TW <= hi;
-    if (whole) {
-        // vector lane + 64 s of the tile: with the swizzle its offset splits into a lane part (one VGPR) and 1024 s (an immediate)
-        const char *const rbase = slab + (SWZ ? result_vec_off8(lane) : 0);
-#pragma unroll
-        for (int s = 0; s < VPL; ++s) {
-            const VT o = SWZ ? *reinterpret_cast<const VT *>(rbase + 1024 * s) : *row_vec(s);
-            st_stream(reinterpret_cast<VT *>(orow + ts) + lane + 64 * s, o);
-        }
-    } else {
-        // first / last tile of a channel (the stored range ends inside it) or unaligned output rows
-        const bool vec = (job.flags & JOB_VEC_OUT) != 0;
-#pragma unroll
-        for (int s = 0; s < VPL; ++s) {
-            const int p = lane + 64 * s;
-            const int g0 = ts + p * E;
-            const VT o = *reinterpret_cast<const VT *>(slab + (SWZ ? result_vec_off8(p) : slab_vec_off<VPL>(p)));
-            if (vec && g0 >= lo && g0 + E <= hi) {
-                *reinterpret_cast<VT *>(orow + g0) = o;
-            } else {
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    if (g0 + e >= lo && g0 + e < hi) orow[g0 + e] = vget(o, e);
-            }
-        }
-    }
+    store_tile<K, SameStorage<T>>(slab, orow, ts, (int)job.store_lo, (int)job.store_hi, job.flags, lane);
     SG_STAMP(4);
 }
 
@@ -649,7 +742,7 @@ __global__ __launch_bounds__(64 * SG_K1D_WAVES, (K1D<float, N, VPL_NARROW>::MIN_
     }
     const int L = (int)job.length;
     const int mode = (int)(job.flags & JOB_MODE_MASK);
-    const unsigned c = job.tpc_shift >= 32 ? tile : (__umulhi(tile, job.tpc_magic) >> job.tpc_shift);
+    const unsigned c = tile_channel(job, tile);
     const int ts = (int)(tile - c * job.tiles_per_channel) * TW;
     const char *__restrict__ row = job.in + (long long)c * job.in_pitch;
     char *__restrict__ orow = job.out + (long long)c * job.out_pitch;

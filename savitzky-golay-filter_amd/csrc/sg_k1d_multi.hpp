@@ -1,10 +1,10 @@
 // sg_k1d_multi.hpp -- the fused multi-output 1-D kernel (savgol_apply_multi_batch_f32): K filters of one half window and one boundary mode
 // (smoothing, d/dt, d^2/dt^2, ...) on ONE read of the input.  Bytes per input sample: 4 + 4 K instead of K (4 + 4).
 //
-// A variant of sg1d_tile_body (sg_k1d.hpp), written beside it so that no existing kernel changes: the same narrow tile (64 lanes x 8 vectors),
-// the same XCD tile order, the same staging of tile + halo into the wave's slab with the same remaps, the same inner product
-// (Conv<float, N, VPL_NARROW>: three interleaved chains) once per output with that output's taps -- so output k carries the bits of the single
-// call with SAVGOL_BATCH_PLAIN_SUMMATION.  Order is what keeps those bits:
+// The tile algorithm of sg1d_tile_body, built from the same pieces (sg_k1d.hpp: sg1d_tile_of_wave, tile_channel, stage_tile, centre_slab, finish_acc,
+// put_results, store_tile) on the narrow tile (64 lanes x 8 vectors), with the same inner product (Conv<float, N, VPL_NARROW>: three interleaved
+// chains) once per output with that output's taps -- so output k carries the bits of the single call with SAVGOL_BATCH_PLAIN_SUMMATION.  Order is
+// what keeps those bits:
 //   1. the outputs that are not centred (derivative 0; the host puts them first, nraw of them) on the RAW slab;
 //   2. then the slab is centred (the single kernel's JOB_CENTRE: the mean of the tile's body, the same Inf / NaN guard), if any output needs it;
 //   3. the centred outputs on the centred slab, each adding back centre * sum(w) and scaling by its own dt_inv.
@@ -34,8 +34,7 @@ template <int N, int K>
 __device__ __forceinline__ void sg1d_multi_body(const JobMulti1D &jm, const TapsMulti &taps)
 {
     typedef K1D<float, N, VPL_NARROW> KT;
-    typedef float4 VT;
-    constexpr int E = KT::E, R = KT::R, TW = KT::TW, NA = KT::NA, HV = KT::HV, VPL = KT::VPL, TV = KT::TV;
+    constexpr int VPL = KT::VPL;
     static_assert(VPL == 8, "the result region uses the swizzled layout of 8 vectors per lane (result_vec_off8)");
     constexpr int RES = 64 * VPL * 16;                                   // bytes of one tile's results
     const Job1D &job = jm.base;
@@ -46,147 +45,39 @@ __device__ __forceinline__ void sg1d_multi_body(const JobMulti1D &jm, const Taps
     char *slab = smem + wave * (KT::SLAB + RES);
     char *res = slab + KT::SLAB;
 
-    // tile order: sg1d_tile_body's (4 waves per block)
-    const unsigned nb8 = gridDim.x >> 3;
-    unsigned blk = blockIdx.x;
-    if (blk < nb8 * 8u) {
-        const unsigned cs = job.xcd_chunk_log2;
-        if (cs == 0) blk = (blk & 7u) * nb8 + (blk >> 3);
-        else if (cs < 32u) {
-            const unsigned span = 8u << cs, q = blk >> (cs + 3u);
-            if ((q + 1u) * span <= nb8 * 8u) { const unsigned r = blk & (span - 1u); blk = (((q << 3) + (r & 7u)) << cs) + (r >> 3); }
-        }
-    }
-    const unsigned tile = blk * KT::WAVES + wave;
+    const unsigned tile = sg1d_tile_of_wave<KT::WAVES>(job, wave);
     if (tile >= job.total_tiles) {
         if (tile - job.total_tiles < job.edge_items) sg1d_multi_edge_item<N, K>(jm, tile - job.total_tiles, lane);
         return;
     }
 
-    const float *__restrict__ gin = static_cast<const float *>(job.in);
-    const int L = (int)job.length;
-    const int mode = (int)(job.flags & JOB_MODE_MASK);
-    const unsigned c = job.tpc_shift >= 32 ? tile : (__umulhi(tile, job.tpc_magic) >> job.tpc_shift);
-    const int ts = (int)(tile - c * job.tiles_per_channel) * TW;
-    const float *__restrict__ row = gin + (long long)c * job.in_ld;
-    char *const slab_row = slab + slab_vec_off<VPL>(lane);
-    auto row_vec = [&](int s) -> VT * { return reinterpret_cast<VT *>(slab_row + s * (16 * (64 + 64 / VPL))); };
+    const unsigned c = tile_channel(job, tile);
+    const int ts = (int)(tile - c * job.tiles_per_channel) * KT::TW;
+    const float *__restrict__ row = static_cast<const float *>(job.in) + (long long)c * job.in_ld;
+    const SlabRows<KT> row_vec(slab, lane);
 
-    // ---- stage tile + halo into the slab: sg1d_tile_body's out-of-place staging, sample for sample ----
-    if ((job.flags & JOB_VEC_IN) && ts - NA >= 0 && ts + TW + NA <= L) {
-        const VT *src = reinterpret_cast<const VT *>(row + (ts - NA));
-        VT p[VPL + 1];
-#pragma unroll
-        for (int s = 0; s < VPL; ++s) p[s] = ld_stream(src + lane + 64 * s);
-        if (lane < 2 * HV) p[VPL] = src[TV + lane];                       // halo: re-read by the neighbour tile, keep it cached
-#pragma unroll
-        for (int s = 0; s < VPL; ++s) *row_vec(s) = p[s];
-        if (lane < 2 * HV) *row_vec(VPL) = p[VPL];
-    } else {
-        const bool vec = (job.flags & JOB_VEC_IN) != 0;
-        const int lim = L + NA;
-#pragma unroll
-        for (int s = 0; s < VPL + 1; ++s) {
-            const int v = lane + 64 * s;
-            const int g0 = ts - NA + v * E;
-            if (v < KT::SV && vec && g0 >= 0 && g0 + E <= L)
-                *reinterpret_cast<VT *>(slab + slab_vec_off<VPL>(v)) = *reinterpret_cast<const VT *>(row + g0);
-        }
-#pragma unroll 4
-        for (int e = lane; e < KT::SL; e += 64) {
-            int g = ts - NA + e;
-            const int g0 = g - (e % E);
-            const bool direct = vec && g0 >= 0 && g0 + E <= L;
-            if (!direct) {
-                float x = 0.0f;
-                if (g < lim) {
-                    bool zero = false;
-                    if (g < 0 || g >= L) g = remap_index(g, L, mode, zero);
-                    if (!zero) x = row[g];
-                }
-                *reinterpret_cast<float *>(slab + slab_vec_off<VPL>(e / E) + (e % E) * (int)sizeof(float)) = x;
-            }
-        }
-    }
+    stage_tile<KT, SameStorage<float>>(row_vec, row, ts, (int)job.length, job.flags, lane);
     wave_lds_sync();
 
-    const int lo = (int)job.store_lo, hi = (int)job.store_hi;
-    const char *const win = slab + 16 * (lane * (VPL + 1));
+    const char *const win = slab + 16 * (lane * (KT::VPL + 1));
     float centre = 0.0f;
     static_for<K>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         if (k == (int)jm.nraw) {
-            // ---- the first centred output: centre the slab as sg1d_tile_body does under JOB_CENTRE (after the raw outputs' window reads) ----
+            // the first centred output: centre the slab, after the raw outputs' window reads
             wave_lds_sync();
-            VT p[VPL + 1];
-            float part = 0.0f;
-#pragma unroll
-            for (int s = 0; s < VPL + 1; ++s) {
-                if (s < VPL || lane < 2 * HV) {
-                    p[s] = *row_vec(s);
-                    const int v = lane + 64 * s;
-                    if (v >= HV && v < HV + TV) {
-#pragma unroll
-                        for (int e = 0; e < E; ++e) part += vget(p[s], e);
-                    }
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-            centre = part * (1.0f / float(TW));
-            if (!(centre - centre == 0.0f)) centre = 0.0f;
-#pragma unroll
-            for (int s = 0; s < VPL + 1; ++s) {
-                if (s < VPL || lane < 2 * HV) {
-#pragma unroll
-                    for (int e = 0; e < E; ++e) vset(p[s], e, vget(p[s], e) - centre);
-                    *row_vec(s) = p[s];
-                }
-            }
+            centre = centre_slab(row_vec, lane);
             wave_lds_sync();
         }
         // ---- output k: the inner product, the centre added back, dt_inv ----
-        const unsigned fk = jm.flags[k];
-        float acc[R];
+        float acc[KT::R];
         Conv<float, N, VPL_NARROW>::run(win, taps.t[k], acc);
-        if (fk & JOB_CENTRE) {
-            const float back = centre * jm.centre_sum[k];
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] += back;
-        }
-        if (fk & JOB_SCALE) {
-            const float s = jm.dt_inv[k];
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] *= s;
-        }
+        finish_acc(acc, jm.flags[k], centre, jm.centre_sum[k], jm.dt_inv[k]);
         // ---- through the result region (the previous output's reads of it are done: one wave's LDS operations run in order) ----
-        {
-            const int wbase = 128 * lane + 16 * (lane & 7);
-#pragma unroll
-            for (int s = 0; s < VPL; ++s) *reinterpret_cast<VT *>(res + (wbase ^ (16 * s))) = float4{acc[4 * s], acc[4 * s + 1], acc[4 * s + 2], acc[4 * s + 3]};
-        }
+        put_results<KT>(res, lane, acc);
         wave_lds_sync();
         float *__restrict__ orow = static_cast<float *>(jm.out[k]) + (long long)c * job.out_ld - (long long)job.out_shift;
-        if ((fk & JOB_VEC_OUT) && ts >= lo && ts + TW <= hi) {
-            const char *const rbase = res + result_vec_off8(lane);
-#pragma unroll
-            for (int s = 0; s < VPL; ++s) st_stream(reinterpret_cast<VT *>(orow + ts) + lane + 64 * s, *reinterpret_cast<const VT *>(rbase + 1024 * s));
-        } else {
-            const bool vec = (fk & JOB_VEC_OUT) != 0;
-#pragma unroll
-            for (int s = 0; s < VPL; ++s) {
-                const int p = lane + 64 * s;
-                const int g0 = ts + p * E;
-                const VT o = *reinterpret_cast<const VT *>(res + result_vec_off8(p));
-                if (vec && g0 >= lo && g0 + E <= hi) {
-                    *reinterpret_cast<VT *>(orow + g0) = o;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < E; ++e)
-                        if (g0 + e >= lo && g0 + e < hi) orow[g0 + e] = vget(o, e);
-                }
-            }
-        }
+        store_tile<KT, SameStorage<float>>(res, orow, ts, (int)job.store_lo, (int)job.store_hi, jm.flags[k], lane);
         wave_lds_sync();
         return true;
     });

@@ -4,7 +4,10 @@ For every half window (m = 4, d = 0, one boundary mode) it times, alternating th
 alone moves the fp32 headline +-3 %): savgol_apply_batch_f32_ex with default flags and with SAVGOL_BATCH_TILE_NARROW, the new call for bf16 -> bf16,
 f16 -> f16 and bf16 -> f32, and savgol_hip_stream_copy of the same 16-bit buffers (the copy ceiling at 4 B per sample).  Prints and writes, per variant:
 ms per launch (median over pairs x reps; min .. max of the per-pair medians), Gsamples/s, the fraction of 8 TB/s at the variant's own bytes per sample, and
-the ratio to the fp32 narrow-tile call.  --only runs one variant alone (counter and trace runs)."""
+the ratio to the fp32 narrow-tile call.  --only runs one variant alone (counter and trace runs).
+   python tools/time_1d_h16.py --libs lib_parent/libsavgol_hip.so lib/libsavgol_hip.so lib_parent/libsavgol_hip.so [--n 5,32]
+instead A/Bs the 16-bit call of several builds (bf16 -> bf16, f16 -> f16, bf16 -> f32) on the same buffers, interleaved inside every repetition
+(tools/ab_libs.py)."""
 import argparse
 import json
 import os
@@ -27,10 +30,13 @@ def main():
     ap.add_argument("--mode", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default="", help="only the variant with this label")
+    ap.add_argument("--libs", nargs="+", default=None, help="A/B the 16-bit call of these builds (list the first one again last for the run's own noise)")
     a = ap.parse_args()
     import torch
     from __graft_entry__ import load_package
     sg = load_package()
+    if a.libs:
+        return ab_libs_main(a, sg, torch)
     L = sg.lib()
     ch, length = a.channels, a.length
     samples = ch * length
@@ -99,6 +105,29 @@ def main():
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+
+
+def ab_libs_main(a, sg, torch):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import ab_libs
+    ch, length = a.channels, a.length
+    x32 = torch.empty((ch, length), dtype=torch.float32, device="cuda")
+    sg.synth(x32)
+    xs = {"f16": x32.to(torch.float16), "bf16": x32.to(torch.bfloat16)}
+    ys = {"f16": torch.empty_like(xs["f16"]), "bf16": torch.empty_like(xs["bf16"]), "f32": x32}      # (x32 is free once it has been narrowed)
+    libs = [ab_libs.load(p) for p in a.libs]
+    st = torch.cuda.current_stream().cuda_stream
+    code = {"f32": sg.SAVGOL_HIP_F32, "f16": sg.SAVGOL_HIP_F16, "bf16": sg.SAVGOL_HIP_BF16}
+    for n in [int(t) for t in a.n.split(",")]:
+        for tin, tout in (("bf16", "bf16"), ("f16", "f16"), ("bf16", "f32")):
+            calls = []
+            for lib in libs:
+                f = ab_libs.new_filter(lib, n, 4, 0, 1.0, a.mode)
+
+                def call(lib=lib, f=f):
+                    assert lib.savgol_apply_batch_h16(f, xs[tin].data_ptr(), code[tin], ys[tout].data_ptr(), code[tout], ch, length, length, length, 0, st) == 0
+                calls.append(call)
+            ab_libs.report(f"h16 {tin}->{tout} n={n}", a.libs, ab_libs.alternate(calls, a.reps))
 
 
 if __name__ == "__main__":

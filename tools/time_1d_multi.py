@@ -3,7 +3,9 @@
 Cases: n = 32, m = 4, d = 0 / 1 / 2 in all four boundary modes (the singles take the block-moment kernel for d <= 1, the plain one for d = 2);
 n = 5, m = 3, d = 0 / 1 / 2 (config 1's filter, batched) and n = 16, m = 4, d = 0 / 1 (count 2), fused with SAVGOL_BATCH_TILE_NARROW -- without it
 their derivative outputs keep the single calls' wide tile and run unfused (include/savgol_hip.h).  Prints ms (median), the speed-up over the single
-calls and the fraction of 8 TB/s at (4 + 4 count) bytes per input sample (the singles' own bytes are count x 8)."""
+calls and the fraction of 8 TB/s at (4 + 4 count) bytes per input sample (the singles' own bytes are count x 8).
+   python tools/time_1d_multi.py --libs lib_parent/libsavgol_hip.so lib/libsavgol_hip.so lib_parent/libsavgol_hip.so [--case ...]
+instead A/Bs the FUSED call of several builds on the same buffers, interleaved inside every repetition (tools/ab_libs.py)."""
 import argparse
 import json
 import os
@@ -24,11 +26,14 @@ def main():
     ap.add_argument("--case", default="", help="only the cases whose label contains this")
     ap.add_argument("--fused-only", action="store_true", help="time only the fused call (counter runs)")
     ap.add_argument("--sweep", action="store_true", help="instead: half windows 4..32, count 2 and 3, against narrow plain-summation single calls")
+    ap.add_argument("--libs", nargs="+", default=None, help="A/B the fused call of these builds (list the first one again last for the run's own noise)")
     a = ap.parse_args()
     import torch
     from __graft_entry__ import load_package
     sg = load_package()
     ch, L = a.channels, a.length
+    if a.libs:
+        return ab_libs_main(a, sg, torch)
     x = torch.empty((ch, L), dtype=torch.float32, device="cuda")
     sg.synth(x)
     outs = [torch.empty_like(x) for _ in range(3)]
@@ -74,6 +79,31 @@ def main():
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(rows, fh, indent=1)
+
+
+def ab_libs_main(a, sg, torch):
+    import ctypes as C
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import ab_libs
+    ch, L = a.channels, a.length
+    x = torch.empty((ch, L), dtype=torch.float32, device="cuda")
+    sg.synth(x)
+    outs = [torch.empty_like(x) for _ in range(3)]
+    libs = [ab_libs.load(p) for p in a.libs]
+    st = torch.cuda.current_stream().cuda_stream
+    for label, n, ds, flags in (("n32 m4 d012", 32, (0, 1, 2), 0), ("n16 m4 d01 narrow", 16, (0, 1), sg.SAVGOL_BATCH_TILE_NARROW), ("n5 m3 d012 narrow", 5, (0, 1, 2), sg.SAVGOL_BATCH_TILE_NARROW)):
+        if a.case not in label:
+            continue
+        k = len(ds)
+        calls = []
+        for lib in libs:
+            fs = (sg._F * k)(*[ab_libs.new_filter(lib, n, 3 if n == 5 else 4, d) for d in ds])
+            ptrs = (C.c_void_p * k)(*[o.data_ptr() for o in outs[:k]])
+
+            def call(lib=lib, fs=fs, ptrs=ptrs):
+                assert lib.savgol_apply_multi_batch_f32(fs, k, x.data_ptr(), ptrs, ch, L, L, L, flags, st) == 0
+            calls.append(call)
+        ab_libs.report(f"multi {label}", a.libs, ab_libs.alternate(calls, a.reps))
 
 
 if __name__ == "__main__":
