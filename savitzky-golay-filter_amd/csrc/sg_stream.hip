@@ -13,8 +13,8 @@
 // Bank layout: ring[slot][stream] (stream fastest), one shared write position because all streams
 // of a bank tick together.  A tick reads ws rows of `streams` floats (coalesced, L2/Infinity-Cache
 // resident: 8.65 MB for 65 536 streams at n=16) and writes one row + one output row.
-// savgol_streambank_push_block keeps each stream's ring in LDS for `ticks` pushes and touches HBM
-// only for the samples and the outputs.
+// savgol_streambank_push_block is a convolution down the tick axis (sg_stream_roll.hip, sg_stream_dma.hip): it reads the
+// samples (and the ring, for the history before the call) and writes the outputs and the ring's newest rows.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -97,34 +97,36 @@ __device__ __forceinline__ void store_out(float *p, float v, bool through)
     else *p = v;
 }
 
-// write one sample per stream at slot wp_old, then (if `emit`) the centre output of the window that
-// now starts at wp_new = (wp_old + 1) % ws
-__global__ __launch_bounds__(256) void sg_bank_tick_kernel(float *__restrict__ ring, const float *__restrict__ samples,
-                                                           float *__restrict__ out, size_t streams,
-                                                           const float *__restrict__ table, int ws, int wp_old,
-                                                           float dt_inv, int emit, const TickSignal sig)
+// a tick while the windows are filling: write one sample per stream at slot wp_old, no output (every tick that has one is dispatch_tick's)
+__global__ __launch_bounds__(256) void sg_bank_tick_kernel(float *__restrict__ ring, const float *__restrict__ samples, size_t streams,
+                                                           int wp_old, const TickSignal sig)
 {
-    __shared__ float wl[SAVGOL_MAX_WINDOW];
-    if (emit) {
-        for (int i = threadIdx.x; i < ws; i += blockDim.x) wl[i] = table[i];
-        __syncthreads();
-    }
     const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < streams) {                                             // (no early return: every thread reaches tick_signal's barrier exactly once)
-        ring[(size_t)wp_old * streams + s] = samples[s];
-        if (emit) {
-            int wp = wp_old + 1;
-            if (wp >= ws) wp -= ws;
-            // the slot just written is read back by the same thread: program order is enough
-            store_out(out + s, __fmul_rn(ring_dot_global(ring, streams, s, wl, ws, wp, false), dt_inv), sig.counter != nullptr);
-        }
-    }
+    if (s < streams) ring[(size_t)wp_old * streams + s] = samples[s];       // (no early return: every thread reaches tick_signal's barrier exactly once)
     tick_signal(sig);
 }
 
 // rows of outputs from the current ring contents: row r uses table row rows[r] (0 = centre,
 // 1+e = edge row e), walked backward (leading edge) or forward
 struct RowList { int count; int row[SAVGOL_MAX_HALF_WINDOW + 1]; int backward[SAVGOL_MAX_HALF_WINDOW + 1]; };
+// the burst of the tick that fills the window: the n leading rows, then the centre -- as many as `max` allows (:205-221); n = 0: the centre alone
+static RowList rows_fill(int n, int max)
+{
+    RowList rows;
+    memset(&rows, 0, sizeof(rows));
+    for (int e = 0; e < n && rows.count < max; ++e) { rows.row[rows.count] = 1 + e; rows.backward[rows.count] = 1; rows.count++; }
+    if (rows.count < max) rows.count++;                                  // row 0, forward
+    return rows;
+}
+// up to `max` of the n edge rows: leading (:269-272; read backwards) or trailing, last output first (:245-249)
+static RowList rows_edge(int n, int max, bool leading, int trail_base)
+{
+    RowList rows;
+    memset(&rows, 0, sizeof(rows));
+    rows.count = max < n ? max : n;
+    for (int i = 0; i < rows.count; ++i) { rows.row[i] = leading ? 1 + i : trail_base + (n - 1 - i); rows.backward[i] = leading ? 1 : 0; }
+    return rows;
+}
 
 __global__ __launch_bounds__(256) void sg_bank_rows_kernel(const float *__restrict__ ring, float *__restrict__ out,
                                                            size_t streams, const float *__restrict__ table, int ws,
@@ -379,8 +381,7 @@ float savgol_stream_push(SavgolStream *stream, float sample, bool *output_valid)
         if (output_valid) *output_valid = false;
         return 0.0f;
     }
-    sg::RowList rows; memset(&rows, 0, sizeof(rows));
-    rows.count = 1;                                              // centre, forward
+    const sg::RowList rows = sg::rows_fill(0, 1);                // centre, forward
     float y = 0.0f;
     if (sg::single_stream_rows(stream, rows, &y) != 0) {
         fprintf(stderr, "savgol_stream_push: %s\n", savgol_hip_last_error());
@@ -399,13 +400,7 @@ int savgol_stream_push_full(SavgolStream *stream, float sample, float *output, i
     const bool was_filling = stream->samples_received < (size_t)ws;
     ring_store(stream, sample);
     if (stream->samples_received < (size_t)ws) return 0;
-    sg::RowList rows; memset(&rows, 0, sizeof(rows));
-    if (was_filling) {                                           // n leading rows, then the centre (:205-221)
-        for (int e = 0; e < n && rows.count < max_outputs; ++e) { rows.row[rows.count] = 1 + e; rows.backward[rows.count] = 1; rows.count++; }
-        if (rows.count < max_outputs) { rows.row[rows.count] = 0; rows.backward[rows.count] = 0; rows.count++; }
-    } else {
-        rows.count = 1;
-    }
+    const sg::RowList rows = sg::rows_fill(was_filling ? n : 0, max_outputs);       // n leading rows, then the centre (:205-221) -- or the centre alone
     float tmp[SAVGOL_MAX_HALF_WINDOW + 1];
     if (sg::single_stream_rows(stream, rows, tmp) != 0) {
         fprintf(stderr, "savgol_stream_push_full: %s\n", savgol_hip_last_error());
@@ -422,9 +417,7 @@ int savgol_stream_flush(SavgolStream *stream, float *output, int max_count)
     const SavgolFilter *f = stream->filter;
     const int n = f->config.half_window;
     if (stream->samples_received < (size_t)f->window_size) return 0;
-    sg::RowList rows; memset(&rows, 0, sizeof(rows));
-    rows.count = max_count < n ? max_count : n;
-    for (int i = 0; i < rows.count; ++i) { rows.row[i] = sg::trailing_row_base(f) + (n - 1 - i); rows.backward[i] = 0; }   // :245-249
+    const sg::RowList rows = sg::rows_edge(n, max_count, false, sg::trailing_row_base(f));
     float tmp[SAVGOL_MAX_HALF_WINDOW + 1];
     if (sg::single_stream_rows(stream, rows, tmp) != 0) {
         fprintf(stderr, "savgol_stream_flush: %s\n", savgol_hip_last_error());
@@ -441,9 +434,7 @@ int savgol_stream_flush_leading(SavgolStream *stream, float *output, int max_cou
     const SavgolFilter *f = stream->filter;
     const int n = f->config.half_window;
     if (stream->samples_received < (size_t)f->window_size) return 0;
-    sg::RowList rows; memset(&rows, 0, sizeof(rows));
-    rows.count = max_count < n ? max_count : n;
-    for (int i = 0; i < rows.count; ++i) { rows.row[i] = 1 + i; rows.backward[i] = 1; }             // :269-272
+    const sg::RowList rows = sg::rows_edge(n, max_count, true, 0);
     float tmp[SAVGOL_MAX_HALF_WINDOW + 1];
     if (sg::single_stream_rows(stream, rows, tmp) != 0) {
         fprintf(stderr, "savgol_stream_flush_leading: %s\n", savgol_hip_last_error());
@@ -568,7 +559,7 @@ static int bank_tick(SavgolStreamBank *bank, const float *d_samples, float *d_ou
                              bank->dt_inv, static_cast<hipStream_t>(stream), sig);
     } else {
         hipLaunchKernelGGL(sg::sg_bank_tick_kernel, dim3(sg::bank_blocks(bank)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           bank->d_ring, d_samples, d_out, bank->streams, bank->d_table, ws, bank->wp, bank->dt_inv, 0, sig);
+                           bank->d_ring, d_samples, bank->streams, bank->wp, sig);
     }
     if (!sg::hip_ok(hipGetLastError(), who)) return -1;
     bank->wp = (bank->wp + 1) % ws;
@@ -652,13 +643,11 @@ int savgol_streambank_push_full(SavgolStreamBank *bank, const float *d_samples, 
         return rc;                                   // 0 while filling, 1 afterwards, -1 on error
     }
     // the tick that completes the window: store the sample, then n leading rows + the centre row
-    hipLaunchKernelGGL(sg::sg_bank_tick_kernel, dim3(sg::bank_blocks(bank)), dim3(256), 0, st, bank->d_ring, d_samples,
-                       d_out, bank->streams, bank->d_table, ws, bank->wp, bank->dt_inv, 0, sg::TickSignal{nullptr, nullptr, 0u});
+    hipLaunchKernelGGL(sg::sg_bank_tick_kernel, dim3(sg::bank_blocks(bank)), dim3(256), 0, st, bank->d_ring, d_samples, bank->streams, bank->wp,
+                       sg::TickSignal{nullptr, nullptr, 0u});
     bank->wp = (bank->wp + 1) % ws;
     bank->received++;
-    sg::RowList rows; memset(&rows, 0, sizeof(rows));
-    for (int e = 0; e < n && rows.count < max_rows; ++e) { rows.row[rows.count] = 1 + e; rows.backward[rows.count] = 1; rows.count++; }
-    if (rows.count < max_rows) { rows.row[rows.count] = 0; rows.backward[rows.count] = 0; rows.count++; }
+    const sg::RowList rows = sg::rows_fill(n, max_rows);
     hipLaunchKernelGGL(sg::sg_bank_rows_kernel, dim3(sg::bank_blocks(bank), rows.count), dim3(256), 0, st, bank->d_ring, d_out,
                        bank->streams, bank->d_table, ws, bank->wp, bank->dt_inv, rows);
     if (!sg::hip_ok(hipGetLastError(), "savgol_streambank_push_full launch")) return -1;
@@ -708,12 +697,7 @@ static int bank_edge_rows(SavgolStreamBank *bank, float *d_out, int max_rows, vo
 {
     const int ws = bank->filter->window_size, n = bank->filter->config.half_window;
     if (bank->received < (unsigned long long)ws) return 0;
-    sg::RowList rows; memset(&rows, 0, sizeof(rows));
-    rows.count = max_rows < n ? max_rows : n;
-    for (int i = 0; i < rows.count; ++i) {
-        rows.row[i] = leading ? 1 + i : bank->trail_base + (n - 1 - i);
-        rows.backward[i] = leading ? 1 : 0;
-    }
+    const sg::RowList rows = sg::rows_edge(n, max_rows, leading, bank->trail_base);
     hipLaunchKernelGGL(sg::sg_bank_rows_kernel, dim3(sg::bank_blocks(bank), rows.count), dim3(256), 0,
                        static_cast<hipStream_t>(stream), bank->d_ring, d_out, bank->streams, bank->d_table, ws, bank->wp,
                        bank->dt_inv, rows);

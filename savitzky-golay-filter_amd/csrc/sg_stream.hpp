@@ -36,7 +36,7 @@ constexpr int STREAM_ROLL_MAX_N = 32;   // the rolling block-push kernel covers 
 constexpr int STREAM_RING_MAX_N = 16;   // ... sample ring (tick loop unrolled 2n+4 times) up to here, accumulator ring above
 
 // sg_stream_roll.hip: `ticks` pushes of every stream in one launch, outputs only (the caller updates the ring).
-// 0 = launched, 1 = not covered (ticks >= 2^31): use the LDS-tiled kernel of sg_stream.hip.
+// 0 = launched, 1 = not covered (half window outside 1..32, ticks >= 2^31: the caller splits longer calls and reports an error otherwise).
 int sg_bank_roll_launch(int n, const float *center_weights, const float *ring, const float *samples, float *out, size_t streams,
                         int wp0, unsigned long long received0, size_t ticks, float dt_inv, int fma, int cu_count, hipStream_t st);
 

@@ -20,7 +20,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 
 #include "sg_internal.h"
@@ -105,17 +104,9 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned nblk = gridDim.x;
-    const unsigned blk = (job.aligned & 2) ? blockIdx.x : (blockIdx.x & 7u) * (nblk >> 3) + (blockIdx.x >> 3);
-    const unsigned t = blk * WPB + (unsigned)wv;                                          // the launch keeps the tile count below 2^31
-    if (t >= (unsigned)geo.total) return;
-    // tile order: groups of `group` neighbouring strips; inside a group band after band, strips fastest (32-bit scalar divisions)
-    const unsigned per_group = geo.group * geo.bands;
-    const unsigned grp = t / per_group;
-    const unsigned rem = t - grp * per_group;
-    const unsigned gs = geo.strips - grp * geo.group < geo.group ? geo.strips - grp * geo.group : geo.group;
-    const unsigned band = rem / gs, strip = grp * geo.group + (rem - band * gs);
-    if (band >= geo.bands) return;
+    const TileAt at = tile_of(geo, xcd_block(job.aligned & 2) * WPB + (unsigned)wv);
+    if (!at.ok) return;
+    const unsigned band = at.band, strip = at.strip;
     const long long t0 = (long long)band * TR;
     const unsigned ring = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)lds) + (unsigned)wv * (unsigned)RING;   // LDS byte address, wave-uniform
     const int sub = lane >> 5, chunk = lane & 31;                                                 // row of the pair, 16-byte chunk of the row
@@ -132,11 +123,7 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
         if (inside) {
             src = p0 + (size_t)i * pstep;
         } else {
-            long long h = t0 - 2 * N + 2 * i + sub;
-            if (h >= (long long)job.ticks) h = (long long)job.ticks - 1;                          // past the call: loaded, never used
-            int slot = job.wp0 + (int)(h < 0 ? h : 0);
-            slot = slot < 0 ? slot + R::WS : slot;
-            src = (h >= 0 ? job.samples + (size_t)h * job.streams : job.ring + (size_t)slot * job.streams) + col;
+            src = history_row<R::WS>(job, t0 - 2 * N + 2 * i + sub) + col;
         }
         dma16(src, ring + (unsigned)(i % DP) * 1024u);
     };
@@ -211,20 +198,11 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
             // the reference's order (src/savgol_stream.c:25-38): sum = 0; sum += w[k] * x[k], k ascending, product and sum rounded separately.
             // Volatile asm for products and sums alike, each product issued one output ahead of its sum: left to the compiler, all the
             // products of a row are hoisted in front of the sums and stay live (256 registers and scratch; see bank_accroll_item)
-            f32x2 p;
-            {
-                constexpr int k0 = r - mlo;
-                if constexpr ((k0 & 1) == 0) asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(p) : "s"(taps.w[k0 >> 1]), "v"(x));
-                else                         asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(p) : "s"(taps.w[k0 >> 1]), "v"(x));
-            }
+            f32x2 p = pk_mul_tap<r - mlo>(taps, x);
             static_for<mhi - mlo + 1>([&](auto ic) -> bool {
                 constexpr int m = mlo + decltype(ic)::value, k = r - m;
                 f32x2 pn = p;
-                if constexpr (m < mhi) {
-                    constexpr int kn = k - 1;
-                    if constexpr ((kn & 1) == 0) asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(pn) : "s"(taps.w[kn >> 1]), "v"(x));
-                    else                         asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(pn) : "s"(taps.w[kn >> 1]), "v"(x));
-                }
+                if constexpr (m < mhi) pn = pk_mul_tap<k - 1>(taps, x);
                 if constexpr (k == 0) asm volatile("v_pk_add_f32 %0, %1, 0 op_sel_hi:[1,0]" : "=v"(acc[0][m]) : "v"(p));       // 0 + p: a product of -0 sums to +0, as in the reference
                 else                  asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc[0][m]) : "v"(p));
                 p = pn;
@@ -237,7 +215,7 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
             if constexpr (CH == 2) a = a + acc[1][m];
 
             const long long tt = t0 + m;
-            const bool has_out = tt < (long long)job.ticks && job.received0 + (unsigned long long)tt + 1 >= (unsigned long long)R::WS;   // uniform (reference :166-170)
+            const bool has_out = tt < (long long)job.ticks && has_output<R::WS>(job, (unsigned long long)tt);                          // uniform
             // fused bank: (a + c * sum_k w_k) * dt_inv in one multiply-add (backdt = c * sum_k w_k * dt_inv, zero unless the tile is centred)
             const f32x2 y = (MOM > 0 || FMA) ? __builtin_elementwise_fma(a, f32x2{job.dt_inv, job.dt_inv}, backdt) : a * f32x2{job.dt_inv, job.dt_inv};
             float *orow = job.out + (size_t)(tt < (long long)job.ticks ? tt : 0) * job.streams;
@@ -263,22 +241,11 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
                 wait_vm<(Q::younger(3, 0) > 63 ? 63 : Q::younger(3, 0))>();
                 static_for<8>([&](auto rc) -> bool { sum = sum + row_in(rc); return true; });
             } else {
-                const long long h0 = -(long long)job.received0;
-                long long h1 = t0 + TR - 1;
-                if (h1 > (long long)job.ticks - 1) h1 = (long long)job.ticks - 1;
-                const int span = (int)(h1 - h0);             // <= 2N + TR - 1
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const long long h = h0 + (span * i) / 7;
-                    const float *src;
-                    if (h >= 0) src = job.samples + (size_t)h * job.streams;
-                    else { int slot = job.wp0 + (int)h; slot = slot < 0 ? slot + R::WS : slot; src = job.ring + (size_t)slot * job.streams; }
-                    sum = sum + *reinterpret_cast<const f32x2 *>(src + (size_t)strip * 128 + 2 * (size_t)lane);
-                }
+                sum = spread_centre<R::WS>(job, t0 - 2 * N, t0 + TR - 1, [&](const float *row) -> f32x2 {
+                    return *reinterpret_cast<const f32x2 *>(row + (size_t)strip * 128 + 2 * (size_t)lane);
+                });
             }
-            cen = sum * f32x2{0.125f, 0.125f};
-            if (!(cen.x - cen.x == 0.0f)) cen.x = 0.0f;           // an Inf / NaN among the eight: that stream's tile stays as it is
-            if (!(cen.y - cen.y == 0.0f)) cen.y = 0.0f;
+            cen = centre_guard(sum);
             backdt = cen * f32x2{job.centre_sum * job.dt_inv, job.centre_sum * job.dt_inv};
         }
     }
@@ -316,41 +283,38 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
     });
 }
 
-template <int N, bool FMA, int TRT, int WPB, int DPR, int FCH = 2>
-[[maybe_unused]] static int launch_bank_dma(const float *center, BankJob job, hipStream_t st)
+// One launch of LDS-DMA tiles (TRT ticks, WPB waves per block, a ring of DP row pairs per wave; group strips per group); 1 = not covered: more tiles
+// than 32 bits index, or a launch the runtime refused -- the caller goes on to the next form
+template <int TRT, int WPB, int DP, class Kernel, class Taps>
+static int launch_dma_tiles(Kernel kernel, unsigned group, BankJob job, const Taps &taps, hipStream_t st)
 {
-    typedef SRoll<N> R;
-    typedef DmaShape<N, TRT> D;
-    SRollTaps<N> taps;
-    memset(&taps, 0, sizeof(taps));
-    for (int k = 0; k < R::WS; ++k) {
-        if (k & 1) taps.w[k >> 1].y = center[k]; else taps.w[k >> 1].x = center[k];
-    }
     TileGeom geo;
-    geo.strips = (unsigned)(job.streams / 128);
-    geo.bands = (unsigned)((job.ticks + D::TR - 1) / D::TR);
-    geo.group = 128u;                                                                            // 64 KiB of a tick row
-    if (geo.group > geo.strips) geo.group = geo.strips;
-    const unsigned groups = (geo.strips + geo.group - 1) / geo.group;
-    geo.total = (unsigned long long)groups * geo.group * geo.bands;
-    const unsigned long long blocks = (geo.total + WPB - 1) / WPB;
-    if (geo.total >= 0x7fffff00ull) return 1;
-    const unsigned grid = ((unsigned)blocks + 7u) & ~7u;
+    const unsigned grid = tile_geom(job.streams, 128, job.ticks, TRT, group, WPB, &geo);
+    if (!grid) return 1;
     job.aligned = 1;
-    constexpr int DP = DPR < D::NI ? DPR : D::NI;                                                 // ring of row pairs (all of the tile's pairs: every load up front)
     constexpr size_t lds = (size_t)WPB * DP * 1024;
     static_assert(lds <= 160 * 1024, "slabs of one block must fit the CU's LDS");
     // more than 64 KiB of dynamic LDS needs the attribute, and the attribute belongs to the (function, DEVICE) pair: set per launch -- a process-wide
     // static applied it on whichever device launched first only (a block push is >= 0.1 ms, the call is host-side bookkeeping)
-    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(sg_bank_dma_kernel<N, FMA, TRT, WPB, DP, FCH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
         return 1;
     }
-    hipLaunchKernelGGL((sg_bank_dma_kernel<N, FMA, TRT, WPB, DP, FCH>), dim3(grid), dim3(64 * WPB), lds, st, job, taps, geo);
-    return hipGetLastError() == hipSuccess ? 0 : 1;                                              // a refused launch = not covered: the caller falls back to the walk
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * WPB), lds, st, job, taps, geo);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 #ifndef SG_DMA_MOM_BUILD
+template <int N, bool FMA, int TRT, int WPB, int DPR, int FCH = 2>
+static int launch_bank_dma(const float *center, const BankJob &job, hipStream_t st)
+{
+    SRollTaps<N> taps;
+    memset(&taps, 0, sizeof(taps));
+    pack_taps(center, SRoll<N>::WS, taps.w);
+    constexpr int DP = DPR < DmaShape<N, TRT>::NI ? DPR : DmaShape<N, TRT>::NI;                   // ring of row pairs (all of the tile's pairs: every load up front)
+    return launch_dma_tiles<TRT, WPB, DP>(sg_bank_dma_kernel<N, FMA, TRT, WPB, DP, FCH>, 128u, job, taps, st);      // groups of 128 strips: 64 KiB of a tick row
+}
+
 template <int N, bool FMA>
 static int launch_bank_dma_shape(const float *center, const BankJob &job, hipStream_t st)
 {
@@ -383,65 +347,37 @@ static int dispatch_bank_dma(int n, int fma, const float *center, const BankJob 
 #define SG_DMA_FN sg_bank_dma_launch_all                     // the Makefile builds two objects (half windows 1..16 and 17..32) with a symbol each
 #endif
 
-// 0 = launched; 1 = not covered: half window outside [SG_DMA_MIN_N, SG_DMA_MAX_N], streams not a multiple of 128, rows not 16-byte aligned or
-// 2 GiB and longer (the store descriptors), or fewer than two tiles of ticks
-int SG_DMA_FN(int n, int fma, const float *center, const BankJob &job, int /*cu_count*/, hipStream_t st)
+// 0 = launched; 1 = not covered (launch_dma_tiles), or a half window outside [SG_DMA_MIN_N, SG_DMA_MAX_N].  The call's shape is block_form's business.
+int SG_DMA_FN(int n, int fma, const float *center, const BankJob &job, hipStream_t st)
 {
     if (n < SG_DMA_MIN_N || n > SG_DMA_MAX_N) return 1;
-    if (job.streams % 128 != 0 || job.streams * 4 >= 0x7fffff00ull) return 1;
-    if (((reinterpret_cast<uintptr_t>(job.samples) | reinterpret_cast<uintptr_t>(job.out) | reinterpret_cast<uintptr_t>(job.ring)) & 15u) != 0) return 1;
-    if (job.ticks < 64) return 1;
     return dispatch_bank_dma<SG_DMA_MIN_N>(n, fma, center, job, st);
 }
 
 #else      // SG_DMA_MOM_BUILD: the third object, block-moment tiles of the fused bank
 template <int N, int M>
-static int launch_bank_dma_mom(const StreamMomentFit &fit, const float *center, BankJob job, hipStream_t st)
+static int launch_bank_dma_mom(const StreamMomentFit &fit, const float *center, const BankJob &job, hipStream_t st)
 {
     // tiles of 32 ticks, (waves per block, ring pairs) = (8, 16): with a third of the arithmetic gone the block-moment tiles want FEWER resident
     // waves with deeper rings -- 8 waves per CU, 16 KiB in flight each (R5.9)
     constexpr int TRT = 32, WPB = 8, DPR = 16;
-    typedef DmaShape<N, TRT> D;
     typedef MomGeom<N> G;
     MomTaps<N, M> taps;
     memset(&taps, 0, sizeof(taps));
-    auto put = [](f32x2 *v, int i, float x) { if (i & 1) v[i >> 1].y = x; else v[i >> 1].x = x; };
-    for (int k = 0; k < 8; ++k) { put(taps.head, k, center[k]); put(taps.tail, k, center[2 * N - 7 + k]); }
-    for (int sm = 0; sm < M; ++sm)
-        for (int off = 0; off < G::NOFF; ++off) put(taps.c[sm], off, fit.c[sm][off]);
-    for (int t = 0; t < 8; ++t) {
-        const float q1 = (float)t - 3.5f;
-        if (M > 1) put(taps.q[0], t, q1);
-        if (M > 2) put(taps.q[M > 2 ? 1 : 0], t, q1 * q1 - 5.25f);
-    }
-    TileGeom geo;
-    geo.strips = (unsigned)(job.streams / 128);
-    geo.bands = (unsigned)((job.ticks + D::TR - 1) / D::TR);
+    pack_taps(center, 8, taps.head);
+    pack_taps(center + 2 * N - 7, 8, taps.tail);
+    for (int sm = 0; sm < M; ++sm) pack_taps(fit.c[sm], G::NOFF, taps.c[sm]);
+    float q[2][8];
+    for (int t = 0; t < 8; ++t) { q[0][t] = (float)t - 3.5f; q[1][t] = q[0][t] * q[0][t] - 5.25f; }
+    for (int sm = 0; sm + 1 < M; ++sm) pack_taps(q[sm], 8, taps.q[sm]);
     // strips per group: 32 KiB of a tick row (64 strips), a quarter of the row for narrow banks.  Measured over FRESH ALLOCATIONS inside one process
     // (tools/placement_stream.py, profiles/r05_placement_stream.txt): with 128-strip groups config 3's launch is 0.363-0.370 ms on most placements of the
     // two buffers and 0.405-0.414 on the rest (3 of 12 to 7 of 12 from call to call); with 64-strip groups 0.373-0.397 on all of them -- the same mean, a
     // third of the spread; 32 768 / 131 072 streams: 0.367 / 0.389 against 0.383 / 0.418; 16 384 streams: 32-strip groups 0.362 against 0.374.  Group sizes
     // that do not divide an XCD's eighth of the tile order (48, 80, 96) cost 10-18 %.  (The tap-by-tap tiles keep 128: the bit-exact bank is 5 % slower on 64.)
-    unsigned want = geo.strips / 4;
-    want = want < 16u ? 16u : (want > 64u ? 64u : want);
-    geo.group = want;
-    if (geo.group > geo.strips) geo.group = geo.strips;
-    const unsigned groups = (geo.strips + geo.group - 1) / geo.group;
-    geo.total = (unsigned long long)groups * geo.group * geo.bands;
-    const unsigned long long blocks = (geo.total + WPB - 1) / WPB;
-    if (geo.total >= 0x7fffff00ull) return 1;
-    const unsigned grid = ((unsigned)blocks + 7u) & ~7u;
-    job.aligned = 1;
-    constexpr int DP = DPR < D::NI ? DPR : D::NI;
-    constexpr size_t lds = (size_t)WPB * DP * 1024;
-    static_assert(lds <= 160 * 1024, "slabs of one block must fit the CU's LDS");
-    auto kernel = sg_bank_dma_kernel<N, true, TRT, WPB, DP, 1, M, MomTaps<N, M>>;
-    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {     // per launch: see launch_bank_dma
-        (void)hipGetLastError();
-        return 1;
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * WPB), lds, st, job, taps, geo);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    const unsigned want = (unsigned)(job.streams / 128 / 4);
+    constexpr int DP = DPR < DmaShape<N, TRT>::NI ? DPR : DmaShape<N, TRT>::NI;
+    return launch_dma_tiles<TRT, WPB, DP>(sg_bank_dma_kernel<N, true, TRT, WPB, DP, 1, M, MomTaps<N, M>>, want < 16u ? 16u : (want > 64u ? 64u : want), job, taps, st);
 }
 
 template <int N>
@@ -456,21 +392,10 @@ static int dispatch_bank_dma_mom(int n, const StreamMomentFit &fit, const float 
     else return 1;
 }
 
-// 0 = launched; 1 = not covered: half window outside 12..20, taps not a polynomial of degree <= 2 (stream_moment_fit), or a shape the tiles do not take
-// (see below).  SAVGOL_HIP_STREAM_MOMENT=0: never (A/B runs against the tap-by-tap tiles).
-int sg_bank_dma_launch_mom(int n, const float *center, const BankJob &job, int /*cu_count*/, hipStream_t st)
+// 0 = launched; 1 = not covered (launch_dma_tiles), or a half window outside 12..20.  `fit`: the host fit of the bank's taps (block_form asked for it)
+int sg_bank_dma_launch_mom(int n, const StreamMomentFit &fit, const float *center, const BankJob &job, hipStream_t st)
 {
-    static const int env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
-    if (!env || n < STREAM_MOMENT_MIN_N || n > STREAM_MOMENT_MAX_N) return 1;
-    if (job.streams % 128 != 0 || job.streams * 4 >= 0x7fffff00ull) return 1;
-    if (((reinterpret_cast<uintptr_t>(job.samples) | reinterpret_cast<uintptr_t>(job.out) | reinterpret_cast<uintptr_t>(job.ring)) & 15u) != 0) return 1;
-    if (job.ticks < 64) return 1;
-    StreamMomentFit fit;
-    if (stream_moment_fit(n, center, &fit) == 0) return 1;
-    // quadratic taps that sum to zero (a second derivative): the outputs are small against the samples, and what the fitted polynomial leaves of the
-    // reference's fp32 taps (<= 3e-7 of the largest) shows in them -- 1.4e-6 of the oracle where the tap-by-tap tiles are at 0.7e-6 and the reference's
-    // own loop at 0.6e-6 (tools/offset_probe_1d.py, R6.16).  Those banks keep the tap-by-tap tiles (7 % slower); config 3's taps are linear.
-    if (job.centre && fit.terms >= 3) return 1;
+    if (n < STREAM_MOMENT_MIN_N || n > STREAM_MOMENT_MAX_N) return 1;
     return dispatch_bank_dma_mom<STREAM_MOMENT_MIN_N>(n, fit, center, job, st);
 }
 

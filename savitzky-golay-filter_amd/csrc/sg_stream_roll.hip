@@ -28,36 +28,29 @@ namespace sg {
 
 // One item: streams s0, s0+1 of every lane, output ticks t0 .. t0+nt-1.  Row r of the band = history index
 // t0 - 2N + r; output tick m needs rows m .. m+2N, row r lives in ring slot r % U.
-// Fused bank, derivative filters (job.centre; sg_stream_dma.hip has the tiles' form and the reasons, R6.16): what an item's rows are centred on -- the mean
-// of eight real samples of each stream, spread from the oldest real one in the item's reach to its last row.  The bit-exact bank and smoothing filters: 0.
+// Fused bank, derivative filters (job.centre; spread_centre): what an item's rows are centred on, from the oldest real sample in the item's reach to
+// its last row.  The bit-exact bank and smoothing filters: 0.
 template <int N, bool VEC, bool FMA>
 __device__ __forceinline__ f32x2 bank_item_centre(const BankJob &job, size_t s0, size_t t0, int nt, bool live0, bool live1)
 {
-    typedef SRoll<N> R;
-    f32x2 cen = f32x2{0.0f, 0.0f};
     if constexpr (FMA) {
         if (job.centre) {                                    // uniform
-            long long h0 = (long long)t0 - 2 * N;
-            if (h0 < -(long long)job.received0) h0 = -(long long)job.received0;
-            long long h1 = (long long)t0 + nt - 1;
-            if (h1 > (long long)job.ticks - 1) h1 = (long long)job.ticks - 1;
-            const long long span = h1 - h0;
-            f32x2 sum = f32x2{0.0f, 0.0f};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const long long h = h0 + (span * i) / 7;
-                int slot = job.wp0 + (int)(h < 0 ? h : 0);
-                slot = slot < 0 ? slot + R::WS : slot;
-                const float *row = h >= 0 ? job.samples + (size_t)h * job.streams : job.ring + (size_t)slot * job.streams;
-                if constexpr (VEC) sum = sum + *reinterpret_cast<const f32x2 *>(row + s0);
-                else sum = sum + f32x2{live0 ? row[s0] : 0.0f, live1 ? row[s0 + 1] : 0.0f};
-            }
-            cen = sum * f32x2{0.125f, 0.125f};
-            if (!(cen.x - cen.x == 0.0f)) cen.x = 0.0f;
-            if (!(cen.y - cen.y == 0.0f)) cen.y = 0.0f;
+            return centre_guard(spread_centre<SRoll<N>::WS>(job, (long long)t0 - 2 * N, (long long)t0 + nt - 1, [&](const float *row) -> f32x2 {
+                if constexpr (VEC) return *reinterpret_cast<const f32x2 *>(row + s0);
+                else return f32x2{live0 ? row[s0] : 0.0f, live1 ? row[s0 + 1] : 0.0f};
+            }));
         }
     }
-    return cen;
+    return f32x2{0.0f, 0.0f};
+}
+
+// row r of an item (history index t0 - 2N + r), the lane's two streams, centred
+template <int N, bool VEC>
+__device__ __forceinline__ f32x2 bank_item_row(const BankJob &job, size_t s0, size_t t0, int r, bool live0, bool live1, const f32x2 cen)
+{
+    const float *row = history_row<SRoll<N>::WS>(job, (long long)t0 - 2 * N + r);
+    if constexpr (VEC) return *reinterpret_cast<const f32x2 *>(row + s0) - cen;
+    else return f32x2{live0 ? row[s0] : 0.0f, live1 ? row[s0 + 1] : 0.0f} - cen;
 }
 
 template <int N, bool VEC, bool FMA>
@@ -67,15 +60,7 @@ __device__ __forceinline__ void bank_roll_item(const BankJob &job, const SRollTa
     const bool live0 = s0 < job.streams, live1 = s0 + 1 < job.streams;
     const f32x2 cen = bank_item_centre<N, VEC, FMA>(job, s0, t0, nt, live0, live1);      // fused bank, derivative filters: what the item's rows are centred on (else 0)
     const f32x2 backdt = cen * f32x2{job.centre_sum * job.dt_inv, job.centre_sum * job.dt_inv};
-    auto load_row = [&](int r) -> f32x2 {
-        long long h = (long long)t0 - 2 * N + r;
-        if (h >= (long long)job.ticks) h = (long long)job.ticks - 1;            // past the call: loaded, never used
-        int slot = job.wp0 + (int)(h < 0 ? h : 0);
-        slot = slot < 0 ? slot + R::WS : slot;
-        const float *row = h >= 0 ? job.samples + (size_t)h * job.streams : job.ring + (size_t)slot * job.streams;
-        if constexpr (VEC) return *reinterpret_cast<const f32x2 *>(row + s0) - cen;
-        else return f32x2{live0 ? row[s0] : 0.0f, live1 ? row[s0 + 1] : 0.0f} - cen;
-    };
+    auto load_row = [&](int r) -> f32x2 { return bank_item_row<N, VEC>(job, s0, t0, r, live0, live1, cen); };
     f32x2 win[R::U];
 #pragma unroll
     for (int r = 0; r < R::U - 1; ++r) win[r] = load_row(r);
@@ -114,7 +99,7 @@ __device__ __forceinline__ void bank_roll_item(const BankJob &job, const SRollTa
             });
             }
             const size_t t = t0 + (size_t)m;
-            if (job.received0 + t + 1 >= (unsigned long long)R::WS) {            // uniform: an output exists (reference :166-170)
+            if (has_output<R::WS>(job, t)) {                                     // uniform
                 const f32x2 y = FMA ? __builtin_elementwise_fma(acc, f32x2{job.dt_inv, job.dt_inv}, backdt) : acc * f32x2{job.dt_inv, job.dt_inv};
                 float *orow = job.out + t * job.streams;
                 if constexpr (VEC) __builtin_nontemporal_store(__builtin_bit_cast(u32x2, y), reinterpret_cast<u32x2 *>(orow + s0));   // written once (round 5: as the LDS-DMA tiles)
@@ -126,10 +111,9 @@ __device__ __forceinline__ void bank_roll_item(const BankJob &job, const SRollTa
 }
 
 // The same item, accumulator stationary (half windows above STREAM_RING_MAX_N, where the unrolled ring of the version
-// above would not fit the instruction cache): 2N accumulator pairs instead of 2N+1 samples live in registers.  Slot a
-// holds the output that has seen a samples so far; an arriving sample is tap a for slot a, and the add writes its sum
-// into slot a+1 (walked from the top down, so that slot is already drained): every output still adds its taps in
-// ascending order onto 0, with separate roundings -- and the tick loop is 2(2N+1) instructions, not unrolled.
+// above would not fit the instruction cache): 2N accumulator pairs instead of 2N+1 samples live in registers and every
+// arriving sample advances all of them by one tap (ref_advance, sg_stream_roll.hpp; the fused bank: one multiply-add
+// per slot) -- the tick loop is 2(2N+1) instructions, not unrolled.
 template <int N, bool VEC, bool FMA>
 __device__ __forceinline__ void bank_accroll_item(const BankJob &job, const SRollTaps<N> &taps, size_t s0, size_t t0, int nt)
 {
@@ -137,15 +121,7 @@ __device__ __forceinline__ void bank_accroll_item(const BankJob &job, const SRol
     const bool live0 = s0 < job.streams, live1 = s0 + 1 < job.streams;
     const f32x2 cen = bank_item_centre<N, VEC, FMA>(job, s0, t0, nt, live0, live1);      // fused bank, derivative filters: what the item's rows are centred on (else 0)
     const f32x2 backdt = cen * f32x2{job.centre_sum * job.dt_inv, job.centre_sum * job.dt_inv};
-    auto load_row = [&](int r) -> f32x2 {
-        long long h = (long long)t0 - 2 * N + r;
-        if (h >= (long long)job.ticks) h = (long long)job.ticks - 1;            // past the call: loaded, never used
-        int slot = job.wp0 + (int)(h < 0 ? h : 0);
-        slot = slot < 0 ? slot + R::WS : slot;
-        const float *row = h >= 0 ? job.samples + (size_t)h * job.streams : job.ring + (size_t)slot * job.streams;
-        if constexpr (VEC) return *reinterpret_cast<const f32x2 *>(row + s0) - cen;
-        else return f32x2{live0 ? row[s0] : 0.0f, live1 ? row[s0 + 1] : 0.0f} - cen;
-    };
+    auto load_row = [&](int r) -> f32x2 { return bank_item_row<N, VEC>(job, s0, t0, r, live0, live1, cen); };
     f32x2 acc[R::WS];                                        // acc[a], a = 1..2N; garbage until a real output reaches it
 #pragma unroll
     for (int a = 0; a < R::WS; ++a) acc[a] = f32x2{0.0f, 0.0f};
@@ -171,9 +147,9 @@ __device__ __forceinline__ void bank_accroll_item(const BankJob &job, const SRol
         // volatile asm, products and adds alike: left to the compiler the adds sink to the end of the iteration and all
         // 2N+1 products stay live (see sg_2d_dense.hip)
         f32x2 done;
-        static_for<R::WS>([&](auto ic) -> bool {
-            constexpr int a = R::WS - 1 - decltype(ic)::value;   // slot = tap index, 2N down to 0
-            if constexpr (FMA) {
+        if constexpr (FMA) {
+            static_for<R::WS>([&](auto ic) -> bool {
+                constexpr int a = R::WS - 1 - decltype(ic)::value;   // slot = tap index, 2N down to 0
                 // fast form: slot a+1 = tap a * x + slot a in ONE instruction (the chain of an output stays a single chain)
                 if constexpr (a == 0) {
                     acc[1] = pk_mul_sgpr<0>(taps.w[0], x);
@@ -186,17 +162,12 @@ __device__ __forceinline__ void bank_accroll_item(const BankJob &job, const SRol
                     else                        asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(acc[a + 1]) : "s"(taps.w[a >> 1]), "v"(x), "v"(acc[a]));
                 }
                 return true;
-            }
-            f32x2 p;
-            if constexpr ((a & 1) == 0) asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(p) : "s"(taps.w[a >> 1]), "v"(x));
-            else                        asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(p) : "s"(taps.w[a >> 1]), "v"(x));
-            if constexpr (a == R::WS - 1)  asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(done) : "v"(acc[a]), "v"(p));
-            else if constexpr (a == 0)     asm volatile("v_pk_add_f32 %0, %1, 0 op_sel_hi:[1,0]" : "=v"(acc[1]) : "v"(p));
-            else                           asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(acc[a + 1]) : "v"(acc[a]), "v"(p));
-            return true;
-        });
+            });
+        } else {
+            done = ref_advance<N>(acc, taps, x);
+        }
         const long long t = (long long)t0 + r - 2 * N;
-        if (r >= 2 * N && job.received0 + (unsigned long long)t + 1 >= (unsigned long long)R::WS) {      // uniform (reference :166-170)
+        if (r >= 2 * N && has_output<R::WS>(job, (unsigned long long)t)) {                               // uniform
             const f32x2 y = FMA ? __builtin_elementwise_fma(done, f32x2{job.dt_inv, job.dt_inv}, backdt) : done * f32x2{job.dt_inv, job.dt_inv};
             float *orow = job.out + (size_t)t * job.streams;
             if constexpr (VEC) __builtin_nontemporal_store(__builtin_bit_cast(u32x2, y), reinterpret_cast<u32x2 *>(orow + s0));
@@ -219,7 +190,6 @@ __device__ __forceinline__ void bank_accroll_item(const BankJob &job, const SRol
 // store nothing; a row without an output selects an empty descriptor), so there is no branch between the first load and the last store
 // and hipcc's vmcnt waits stay counted.
 // Tiles of 16 tick rows, 2 waves per block.
-constexpr int STREAM_TILE_ROWS = 16, STREAM_TILE_WPB = 2;
 template <int N, bool FMA>
 __global__ __launch_bounds__(64 * STREAM_TILE_WPB, 2) void sg_bank_tile_kernel(const BankJob job, const SRollTaps<N> taps, const TileGeom geo)
 {
@@ -227,28 +197,16 @@ __global__ __launch_bounds__(64 * STREAM_TILE_WPB, 2) void sg_bank_tile_kernel(c
     constexpr int TR = STREAM_TILE_ROWS, ROWS = TR + 2 * N, NP = 2;        // NP: stream pairs of a lane's 16-byte quad
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned nblk = gridDim.x;
-    const unsigned blk = (job.aligned & 2) ? blockIdx.x : (blockIdx.x & 7u) * (nblk >> 3) + (blockIdx.x >> 3);
-    const unsigned long long t = (unsigned long long)blk * STREAM_TILE_WPB + (unsigned)wv;
-    if (t >= geo.total) return;
-    // tile order: groups of `group` neighbouring strips; inside a group band after band, strips fastest
-    const unsigned long long per_group = (unsigned long long)geo.group * geo.bands;
-    const unsigned grp = (unsigned)(t / per_group);
-    const unsigned long long rem = t % per_group;
-    const unsigned gs = geo.strips - grp * geo.group < geo.group ? geo.strips - grp * geo.group : geo.group;     // strips in this (last) group
-    const unsigned band = (unsigned)(rem / gs), strip = grp * geo.group + (unsigned)(rem % gs);
-    if (band >= geo.bands) return;                                       // the last group is narrower: its tail of the t range is empty
+    const TileAt at = tile_of(geo, xcd_block(job.aligned & 2) * STREAM_TILE_WPB + (unsigned)wv);
+    if (!at.ok) return;
+    const unsigned band = at.band, strip = at.strip;
     const size_t t0 = (size_t)band * TR;
     const unsigned voff = (strip * 256u + 4u * (unsigned)lane) * 4u;      // byte offset of this lane's streams in a row
     const int row_bytes = (int)(job.streams * 4);
 
     struct Row { f32x2 p[NP]; };
     auto load_row = [&](int r) -> Row {
-        long long h = (long long)t0 - 2 * N + r;
-        if (h >= (long long)job.ticks) h = (long long)job.ticks - 1;            // past the call: loaded, never used
-        int slot = job.wp0 + (int)(h < 0 ? h : 0);
-        slot = slot < 0 ? slot + R::WS : slot;
-        const float *row = h >= 0 ? job.samples + (size_t)h * job.streams : job.ring + (size_t)slot * job.streams;
+        const float *row = history_row<R::WS>(job, (long long)t0 - 2 * N + r);
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, row_bytes, 0x00020000);
         const f32x4 q = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
         Row o;
@@ -296,7 +254,7 @@ __global__ __launch_bounds__(64 * STREAM_TILE_WPB, 2) void sg_bank_tile_kernel(c
             });
         }
         const size_t tt = t0 + (size_t)m;
-        const bool has_out = tt < job.ticks && job.received0 + tt + 1 >= (unsigned long long)R::WS;     // uniform (reference :166-170)
+        const bool has_out = tt < job.ticks && has_output<R::WS>(job, tt);                               // uniform
         const f32x2 s = f32x2{job.dt_inv, job.dt_inv};
         float *orow = job.out + (tt < job.ticks ? tt : 0) * job.streams;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(orow, 0, has_out ? row_bytes : 0, 0x00020000);
@@ -313,7 +271,7 @@ __global__ __launch_bounds__(256) void sg_bank_roll_kernel(const BankJob job, co
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // persistent waves; the 4 waves of a block take adjacent strips (2 KB contiguous per tick row)
     const unsigned nblk = gridDim.x;
-    const unsigned blk = (job.aligned & 2) ? blockIdx.x : (blockIdx.x & 7u) * (nblk >> 3) + (blockIdx.x >> 3);      // bit 1: launch order (launch_bank_roll always sets it)
+    const unsigned blk = xcd_block(job.aligned & 2);         // (launch_bank_roll always asks for launch order)
     const unsigned long long total = (unsigned long long)job.strips * job.bands;
     for (unsigned long long item = (unsigned long long)blk * 4u + (unsigned)wv; item < total; item += (unsigned long long)nblk * 4u) {
         const unsigned strip = (unsigned)(item % job.strips), band = (unsigned)(item / job.strips);
@@ -329,15 +287,32 @@ __global__ __launch_bounds__(256) void sg_bank_roll_kernel(const BankJob job, co
     }
 }
 
+// register tiles (half windows <= 12 of the bit-exact bank: block_form): groups of 64 strips -- (TR + 2N) rows x 64 KiB of a tick row stay well inside
+// an XCD's 4 MiB L2 beside the rows in flight
+template <int N>
+static int dispatch_bank_tile(int n, const float *center, BankJob job, hipStream_t st)
+{
+    if (n == N) {
+        SRollTaps<N> taps;
+        memset(&taps, 0, sizeof(taps));
+        pack_taps(center, SRoll<N>::WS, taps.w);
+        TileGeom geo;
+        const unsigned grid = tile_geom(job.streams, 256, job.ticks, STREAM_TILE_ROWS, 64, STREAM_TILE_WPB, &geo);
+        if (!grid) return 1;
+        job.aligned = 1;
+        hipLaunchKernelGGL((sg_bank_tile_kernel<N, false>), dim3(grid), dim3(64 * STREAM_TILE_WPB), 0, st, job, taps, geo);
+        return 0;
+    }
+    if constexpr (N < 12) return dispatch_bank_tile<N + 1>(n, center, job, st);
+    else return 1;
+}
+
 template <int N, bool FMA>
 static int launch_bank_roll(const float *center, BankJob job, int cu_count, hipStream_t st)
 {
-    typedef SRoll<N> R;
     SRollTaps<N> taps;
     memset(&taps, 0, sizeof(taps));
-    for (int k = 0; k < R::WS; ++k) {
-        if (k & 1) taps.w[k >> 1].y = center[k]; else taps.w[k >> 1].x = center[k];
-    }
+    pack_taps(center, SRoll<N>::WS, taps.w);
     static const int per_cu = [] {                           // resident blocks per CU of this instantiation
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sg_bank_roll_kernel<N, FMA>, 256, 0) != hipSuccess || nb < 1) nb = 2;
@@ -345,62 +320,9 @@ static int launch_bank_roll(const float *center, BankJob job, int cu_count, hipS
         if (FMA && N <= 16 && nb > 2) nb = 2;                // fewer waves, more rows in flight each (see SRoll::P)
         return nb;
     }();
-    // Where the tile form pays (profiles/r04_stream_tile.txt; config 3's shape, 65 536 streams x 4096 ... 16 384 ticks, five variants of
-    // streams per lane x rows per tile x waves per block, strips per group 8 ... 256): the reference-order bank at n <= 12 (n = 4: 0.393 vs
-    // 0.420 ms, n = 8: 0.408 vs 0.425); at n = 16 its 2n = 32 halo rows per 16-row tile (3 x the row reads out of L2) cancel the gain
-    // (0.44-0.47 vs 0.45-0.46), and the fused multiply-add bank's walk is level or ahead at every half window (n = 16: 0.400-0.425 vs
-    // 0.403-0.446).  Both forms sit at 0.60-0.69 of the roofline on this 2 GB call, a 0.4 ms launch, whatever the call's length.
-    if constexpr (N <= 12 && !FMA) {
-        // the tile form: rows of whole 16-byte quads (the buffer range check works on whole accesses), rows < 2 GiB, at least two tiles of ticks
-        const bool quads = job.streams % 4 == 0 && job.streams * 4 < 0x7fffff00ull &&
-                           ((reinterpret_cast<uintptr_t>(job.samples) | reinterpret_cast<uintptr_t>(job.out) | reinterpret_cast<uintptr_t>(job.ring)) & 15u) == 0;
-        if (quads && job.ticks >= 2 * STREAM_TILE_ROWS) {
-            TileGeom geo;
-            geo.strips = (unsigned)((job.streams + 255) / 256);
-            geo.bands = (unsigned)((job.ticks + STREAM_TILE_ROWS - 1) / STREAM_TILE_ROWS);
-            // strips per group: (TR + 2N) rows x group KiB should stay well inside an XCD's 4 MiB L2 beside the rows in flight
-            geo.group = 64;                          // 64 KiB of a tick row
-            if (geo.group > geo.strips) geo.group = geo.strips;
-            const unsigned groups = (geo.strips + geo.group - 1) / geo.group;
-            geo.total = (unsigned long long)groups * geo.group * geo.bands;
-            const unsigned long long blocks = (geo.total + STREAM_TILE_WPB - 1) / STREAM_TILE_WPB;
-            if (blocks < 0x7fffff00ull) {
-                unsigned grid = ((unsigned)blocks + 7u) & ~7u;
-                job.aligned = 1;
-                hipLaunchKernelGGL((sg_bank_tile_kernel<N, FMA>), dim3(grid), dim3(64 * STREAM_TILE_WPB), 0, st, job, taps, geo);
-                return 0;
-            }
-        }
-    }
     const unsigned nwaves = (unsigned)cu_count * (unsigned)per_cu * 4u;
     job.strips = (unsigned)((job.streams + 127) / 128);
-    // Bands of ticks: the resident waves take the strips x bands items round robin, so the call lasts (rounds of items) x (rows per band +
-    // 2n warm-up rows).  Rounds 1-3 took ceil(waves / strips) bands, which is right when the strips divide the waves (65 536 streams: 512
-    // strips, 4 bands, one round) and badly wrong next to it: 66 560 streams = 520 strips x 4 bands = 2080 items on 2048 waves -- a second
-    // round for 32 items, 0.595 ms where 65 536 streams take 0.44.  Now the band count with the cheapest (rounds x rows) is taken
-    // (a band re-reads 2n warm-up rows: keep it >= 8 windows).
-    const size_t max_bands = job.ticks / (size_t)(8 * R::WS) > 0 ? job.ticks / (size_t)(8 * R::WS) : 1;
-    size_t bands = 1;
-    {
-        // Candidates: every count up to the one that gives each resident wave an item (ceil(waves / strips), what rounds 1-3 took), bounded
-        // by max_bands.  (round 4 stopped the search at 64, so a bank of FEW strips and a long block -- 1024 streams = 8 strips
-        // x 100 000 ticks -- ran on 512 of its 2048 waves; the search is coarse above 64 to stay a few hundred steps.)
-        double best = 1e300;
-        const size_t fill = (nwaves + job.strips - 1) / (size_t)job.strips;
-        size_t top = fill > 64 ? fill : 64;
-        if (top > max_bands) top = max_bands;
-        for (size_t b = 1; b <= top; b += (b < 64 ? 1 : (b / 64 < 1 ? 1 : b / 64))) {
-            const size_t rows = (job.ticks + b - 1) / b + 2 * (size_t)N;
-            const size_t rounds = ((size_t)job.strips * b + nwaves - 1) / nwaves;
-            const double cost = (double)rounds * (double)rows;
-            if (cost < best * 0.999) { best = cost; bands = b; }
-        }
-        if (top > 64) {                                      // the exact fill count is always a candidate
-            const size_t b = top;
-            const double cost = (double)(((size_t)job.strips * b + nwaves - 1) / nwaves) * (double)((job.ticks + b - 1) / b + 2 * (size_t)N);
-            if (cost < best * 0.999) { best = cost; bands = b; }
-        }
-    }
+    const size_t bands = walk_bands(job.ticks, job.strips, nwaves, N);
     job.band_ticks = (int)((job.ticks + bands - 1) / bands);
     job.bands = (unsigned)((job.ticks + (size_t)job.band_ticks - 1) / (size_t)job.band_ticks);
     const unsigned long long total = (unsigned long long)job.strips * job.bands;
@@ -422,7 +344,8 @@ static int dispatch_bank_roll(int n, int fma, const float *center, const BankJob
     else return 1;
 }
 
-// 0 = launched, 1 = half window not covered (the caller uses the LDS-tiled kernel).  ticks per call < 2^31 * band.
+// 0 = launched, 1 = not covered (half window outside 1..32, ticks >= 2^31).  Builds the job, asks block_form (sg_stream_host.hpp) which form the call
+// takes and launches it; a launcher that reports "not covered" hands the call to the next form.
 int sg_bank_roll_launch(int n, const float *center_weights, const float *ring, const float *samples, float *out, size_t streams,
                         int wp0, unsigned long long received0, size_t ticks, float dt_inv, int fma, int cu_count, hipStream_t st)
 {
@@ -437,10 +360,21 @@ int sg_bank_roll_launch(int n, const float *center_weights, const float *ring, c
         job.centre_sum = (float)wsum;
         job.centre = (fma && std::fabs(wsum) < 1e-3 * wabs) ? 1 : 0;       // smoothing filters (sum 1) gain nothing and a zero-mean stream would lose
     }
-    // round 5: the LDS-DMA tile form where it covers the call (sg_stream_dma.hip; SAVGOL_HIP_STREAM_DMA=0 for A/B runs against the forms below)
     static const int dma_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }();
-    if (dma_env && sg_bank_dma_launch(n, fma, center_weights, job, cu_count, st) == 0) return 0;
-    return dispatch_bank_roll<1>(n, fma, center_weights, job, cu_count, st);
+    static const int moment_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
+    const unsigned misaligned = (unsigned)((reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ring)) & 15u);
+    StreamMomentFit fit;
+    for (int first = MOMENT_TILES;; ++first) {
+        const BlockForm form = block_form(n, fma != 0, streams, ticks, misaligned, job.centre != 0, dma_env != 0, moment_env != 0,
+                                          [&] { return stream_moment_fit(n, center_weights, &fit); }, first);
+        switch (form) {
+        case MOMENT_TILES:   if (sg_bank_dma_launch_mom(n, fit, center_weights, job, st) == 0) return 0; break;
+        case DMA_TILES:      if ((n <= 16 ? sg_bank_dma_launch_lo : sg_bank_dma_launch_hi)(n, fma, center_weights, job, st) == 0) return 0; break;
+        case REGISTER_TILES: if (dispatch_bank_tile<1>(n, center_weights, job, st) == 0) return 0; break;
+        case WALK:           return dispatch_bank_roll<1>(n, fma, center_weights, job, cu_count, st);
+        }
+        first = form;                                        // not covered: the next form in the order
+    }
 }
 
 }  // namespace sg

@@ -11,7 +11,7 @@
 //             in HBM, then writes the sequence number into ITS word of a done array in pinned host memory
 //     host  : spins on the done array until every wave has reported
 // No launch, no stream synchronise, no atomics.  Arithmetic per output is the reference's, exactly as in the block-push kernel
-// (sg_stream_roll.hip, bank_accroll_item): one accumulator starting at 0, taps ascending, multiply and add rounded separately,
+// (ref_advance, sg_stream_roll.hpp: the step bank_accroll_item takes too): one accumulator starting at 0, taps ascending, multiply and add rounded separately,
 // then * dt_inv -> bit-identical to savgol_stream_push (reference src/savgol_stream.c:25-38, 152-178).
 // The ring in HBM is kept current every tick, so stopping the service (or its idle time-out) needs no state hand-back: the
 // stream-ordered calls (push, push_block, flush, save ...) continue from where the service stopped.
@@ -38,6 +38,7 @@
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
 #include "sg_stream.hpp"
+#include "sg_stream_roll.hpp"
 
 namespace sg {
 
@@ -71,8 +72,6 @@ struct ServiceArgs {
     unsigned long long idle_ticks;                           // s_memrealtime ticks (100 MHz) without a doorbell before a wave leaves
 };
 
-template <int N> struct ServiceTaps { f32x2 w[N + 1]; };
-
 __device__ __forceinline__ f32x4 load16_system(const float *p)
 {
     f32x4 v;
@@ -84,28 +83,8 @@ __device__ __forceinline__ void store16_system(float *p, const f32x4 v)
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(p), "v"(v) : "memory");
 }
 
-// every accumulator one tap further with sample pair x: slot a holds the output that has seen a samples; w[a]*x is added and
-// the sum moves to slot a+1 (walked from the top down).  Returns the output that has just seen its last tap.
 template <int N>
-__device__ __forceinline__ f32x2 advance(f32x2 (&acc)[2 * N + 1], const ServiceTaps<N> &taps, const f32x2 x)
-{
-    constexpr int WS = 2 * N + 1;
-    f32x2 done;
-    static_for<WS>([&](auto ic) -> bool {
-        constexpr int a = WS - 1 - decltype(ic)::value;
-        f32x2 p;
-        if constexpr ((a & 1) == 0) asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(p) : "s"(taps.w[a >> 1]), "v"(x));
-        else                        asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(p) : "s"(taps.w[a >> 1]), "v"(x));
-        if constexpr (a == WS - 1)  asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(done) : "v"(acc[a]), "v"(p));
-        else if constexpr (a == 0)  asm volatile("v_pk_add_f32 %0, %1, 0 op_sel_hi:[1,0]" : "=v"(acc[1]) : "v"(p));
-        else                        asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(acc[a + 1]) : "v"(acc[a]), "v"(p));
-        return true;
-    });
-    return done;
-}
-
-template <int N>
-__global__ __launch_bounds__(64) void sg_bank_service_kernel(const ServiceArgs a, const ServiceTaps<N> taps)
+__global__ __launch_bounds__(64) void sg_bank_service_kernel(const ServiceArgs a, const SRollTaps<N> taps)
 {
     constexpr int WS = 2 * N + 1;
     const int lane = threadIdx.x;
@@ -124,8 +103,8 @@ __global__ __launch_bounds__(64) void sg_bank_service_kernel(const ServiceArgs a
         slot = slot < 0 ? slot + WS : slot;
         f32x4 x = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         if (live) x = *reinterpret_cast<const f32x4 *>(a.ring + (size_t)slot * a.streams + s0);
-        (void)advance<N>(acc0, taps, f32x2{x.x, x.y});
-        (void)advance<N>(acc1, taps, f32x2{x.z, x.w});
+        (void)ref_advance<N>(acc0, taps, f32x2{x.x, x.y});
+        (void)ref_advance<N>(acc1, taps, f32x2{x.z, x.w});
     }
 
     int wp = a.wp0;
@@ -152,8 +131,8 @@ __global__ __launch_bounds__(64) void sg_bank_service_kernel(const ServiceArgs a
         ++received;
         if (live) {
             const f32x4 x = load16_system(in + s0);
-            const f32x2 y0 = advance<N>(acc0, taps, f32x2{x.x, x.y});
-            const f32x2 y1 = advance<N>(acc1, taps, f32x2{x.z, x.w});
+            const f32x2 y0 = ref_advance<N>(acc0, taps, f32x2{x.x, x.y});
+            const f32x2 y1 = ref_advance<N>(acc1, taps, f32x2{x.z, x.w});
             if (received >= (unsigned long long)WS) {        // uniform: the windows are full (reference :166-170)
                 const f32x2 o0 = y0 * s2, o1 = y1 * s2;
                 store16_system(out + s0, f32x4{o0.x, o0.y, o1.x, o1.y});
@@ -187,9 +166,9 @@ template <int N>
 static bool launch_service(int n, const ServiceArgs &args, const float *cw, unsigned waves, hipStream_t st)
 {
     if (n == N) {
-        ServiceTaps<N> taps;
+        SRollTaps<N> taps;
         memset(&taps, 0, sizeof(taps));
-        for (int k = 0; k < 2 * N + 1; ++k) { if (k & 1) taps.w[k >> 1].y = cw[k]; else taps.w[k >> 1].x = cw[k]; }
+        pack_taps(cw, 2 * N + 1, taps.w);
         hipLaunchKernelGGL((sg_bank_service_kernel<N>), dim3(waves), dim3(64), 0, st, args, taps);
         return true;
     }

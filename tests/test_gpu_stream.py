@@ -162,14 +162,11 @@ def test_stream_bank_bit_exact_vs_oracle(sg, sgo, torch_gpu, cfg):
         assert same_bits(np.array([v for v, ok in seq if ok], np.float32), centre[:, s])
 
 
-@pytest.mark.parametrize("n", list(range(1, 18)) + [32])
-def test_block_push_equals_tick_pushes_every_half_window(sg, torch_gpu, n):
-    """push_block (rolling-window kernel for n <= 16, LDS-tiled kernel above) against the per-tick push kernel, which the
-    test above pins to the oracle: every stream, bit for bit.  Odd stream counts and a misaligned sample pointer take
-    the scalar path; a partly filled ring, a wrapped ring and several row bands per call are all in the sequence."""
-    torch = torch_gpu
+def block_pushes_equal_tick_pushes(sg, torch, n, shapes):
+    """push_block against the per-tick push kernel on (streams, pointer offset in floats) shapes: every stream, bit for bit, counters included.
+    The cuts put a partly filled ring, a ring that has just filled, a wrapped ring and a call of several row bands / tiles into the sequence."""
     m = min(3, 2 * n)
-    for S, off in ((777, 1), (1024, 0)):
+    for S, off in shapes:
         T = 40 * (2 * n + 1) + 7
         g = torch.Generator(device="cuda").manual_seed(n * 1000 + S)
         flat = torch.randn(T * S + 4, generator=g, device="cuda", dtype=torch.float32)
@@ -199,6 +196,22 @@ def test_block_push_equals_tick_pushes_every_half_window(sg, torch_gpu, n):
         assert torch.isnan(got[:2 * n]).all() and torch.isnan(want[:2 * n]).all()
         assert torch.equal(got[2 * n:].view(torch.int32), want[2 * n:].view(torch.int32)), (n, S)
         assert bank.counters == ref.counters
+
+
+@pytest.mark.parametrize("n", list(range(1, 18)) + [19, 20, 24, 32])
+def test_block_push_equals_tick_pushes_every_half_window(sg, torch_gpu, n):
+    """push_block of the bit-exact bank against the per-tick push kernel, which the test above pins to the oracle: every stream, bit for bit.
+    777 streams behind a misaligned sample pointer take the walk's element path (sample ring for n <= 16, accumulator ring above); 1024 aligned
+    streams take the LDS-DMA tiles for n <= 16 and from n = 20, and the walk's 8-byte path for n = 17..19 -- the calls shorter than 64 ticks
+    (the filling ring) the register tiles (n <= 12) or the walk."""
+    block_pushes_equal_tick_pushes(sg, torch_gpu, n, ((777, 1), (1024, 0)))
+
+
+@pytest.mark.parametrize("n", [1, 12, 13])
+def test_block_push_register_tiles_equal_tick_pushes(sg, torch_gpu, n):
+    """260 aligned streams are whole 16-byte quads but not whole 128-stream strips: the bit-exact bank takes the register tiles for n <= 12
+    (two strips of 256 streams, the second with four live streams) and the walk for n = 13.  Same cuts and comparison as the test above."""
+    block_pushes_equal_tick_pushes(sg, torch_gpu, n, ((260, 0),))
 
 
 def test_stream_bank_config3_shape(sg, sgo, torch_gpu):
