@@ -249,13 +249,47 @@ int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int c
  * that share a byte (in place included: a 16-bit row cannot hold its fp32 halo stash; use separate buffers).
  * Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for 16-bit rows, 16 for fp32 output) move as vectors; any
  * other base or pitch is served element by element.  Like the single calls it only enqueues (after one warm-up call with the same filter), so it
- * can be captured into a graph.  Not served in 16 bit: the strided, multi-output, stream-bank and 2-D paths, int16 samples, fp32 -> 16-bit pairs. */
+ * can be captured into a graph.  Several filters on one read of 16-bit rows: savgol_apply[_valid]_multi_batch_h16 below.  Not served in 16 bit: the strided, stream-bank and 2-D
+ * paths, int16 samples, fp32 -> 16-bit pairs. */
 enum { SAVGOL_HIP_F32 = 0, SAVGOL_HIP_F16 = 1, SAVGOL_HIP_BF16 = 2 };   /* storage type of a device buffer */
 int savgol_apply_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
                            size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
 /* the same with savgol_apply_valid's outputs: length - 2n elements at d_out[c*out_ld + 0..] */
 int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
                                  size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
+
+/* Several filters on ONE batch of 16-bit rows in one pass: the multi-output call on 16-bit storage.  2 + 2 count bytes per input sample
+ * (16 -> 16 bit) instead of count x 4 for count single calls; 8 bytes for a smoothed trace and two derivatives.
+ * `filters` and `d_outs` are host arrays of `count` entries, 1 <= count <= SAVGOL_MULTI_MAX_FILTERS, as in savgol_apply_multi_batch_f32; all filters
+ * share config.half_window and config.boundary.  d_in holds rows of `in_type` elements; EVERY output holds rows of `out_type` elements with the one
+ * pitch out_ld; in_ld and out_ld count elements of their own buffer's type.  Type pairs are those of savgol_apply_batch_h16: f16 -> f16,
+ * bf16 -> bf16, f16 -> f32, bf16 -> f32.
+ * CONTRACT: output k equals, bit for bit,
+ *   savgol_apply[_valid]_batch_h16(filters[k], d_in, in_type, d_outs[k], out_type, ..., flags | SAVGOL_BATCH_PLAIN_SUMMATION, stream)
+ * and, equivalently, output k of savgol_apply[_valid]_multi_batch_f32(filters, widen(d_in), ..., flags | SAVGOL_BATCH_TILE_NARROW) rounded ONCE to
+ * nearest even into out_type (for out_type f32: that output itself).  NaN positions coincide; NaN payloads are free.
+ * `flags` is a complete SAVGOL_BATCH_* word: SAVGOL_BATCH_PLAIN_SUMMATION (implied), SAVGOL_BATCH_TILE_NARROW (implied) and
+ * SAVGOL_BATCH_CORRECT_LEADING_EDGE are served.  The narrow tile is implied, so the fp32 call's wide-tile exception does not exist here: every
+ * output fuses.  2 or 3 outputs are one launch, 4 are two launches of two (the input is read twice), 1 is the single 16-bit call with
+ * SAVGOL_BATCH_PLAIN_SUMMATION.  Outputs land in the caller's order.
+ * Returns -1 with a text naming the call, before any device call; the checks run in this order and the first fault wins:
+ *   1. flags: SAVGOL_BATCH_REFERENCE_SUMMATION, then SAVGOL_BATCH_TILE_WIDE, then flags of other calls (BOUNDARY_AWARE, MOMENT_F64), then unknown bits;
+ *   2. an unserved type pair;
+ *   3. a NULL `filters`, `d_outs` or `d_in`;   4. count outside 1..4;   5. a NULL or malformed filters[k] / a NULL d_outs[k], k ascending;
+ *   6. filters[k] with another half_window, then another boundary, than filters[0], k ascending;
+ *   7. length < window, then channels longer than 2^30 samples, then a pitch smaller than the row;
+ *   8. for k ascending: d_outs[k] sharing a byte with the input rows, then with the rows of d_outs[j], j < k (compared byte-wise: the element
+ *      sizes may differ; in place is not served).
+ * Like its siblings it only enqueues (after one warm-up call with the same filters), so it can be captured into a graph. */
+int savgol_apply_multi_batch_h16(const SavgolFilter *const *filters, int count,
+                                 const void *d_in, int in_type, void *const *d_outs, int out_type,
+                                 size_t channels, size_t length, size_t in_ld, size_t out_ld,
+                                 unsigned flags, void *stream);
+/* the same with savgol_apply_valid's outputs: length - 2n elements at d_outs[k][c*out_ld + 0..] */
+int savgol_apply_valid_multi_batch_h16(const SavgolFilter *const *filters, int count,
+                                       const void *d_in, int in_type, void *const *d_outs, int out_type,
+                                       size_t channels, size_t length, size_t in_ld, size_t out_ld,
+                                       unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------- stream bank --------- *
  * `streams` independent SavgolStream-equivalents advancing in lock step, state in HBM as a

@@ -130,6 +130,8 @@ SIGNATURES = {
     "savgol_apply_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_multi_batch_h16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.c_int, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_valid_multi_batch_h16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.c_int, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_hip_default_flags": (C.c_uint, []),
     # savgol_hip.h: stream bank
@@ -336,30 +338,48 @@ class Filter:
         return y
 
 
-def apply_multi_batch(filters, d_in, d_outs, channels, length, in_ld=None, out_ld=None, flags=0, valid=False, stream=None):
+def apply_multi_batch(filters, d_in, d_outs, channels, length, in_ld=None, out_ld=None, flags=0, valid=False, stream=None, dtype="f32", out_dtype=None):
     """savgol_apply[_valid]_multi_batch_f32: several Filters of one half window and boundary on one read of d_in (fp32 device memory).
-    d_outs[k] receives filters[k]'s output, bit-identical to filters[k].apply_batch(..., flags=flags | SAVGOL_BATCH_PLAIN_SUMMATION)."""
+    d_outs[k] receives filters[k]'s output, bit-identical to filters[k].apply_batch(..., flags=flags | SAVGOL_BATCH_PLAIN_SUMMATION).
+    dtype "f16" / "bf16": savgol_apply[_valid]_multi_batch_h16 -- 16-bit rows in, every output of out_dtype (None = the same type, or "f32"); in_ld /
+    out_ld count elements of their own buffer; d_outs[k] is bit-identical to filters[k].apply_batch(..., dtype=dtype, out_dtype=out_dtype,
+    flags=flags | SAVGOL_BATCH_PLAIN_SUMMATION)."""
     count = len(filters)
     if len(d_outs) != count:
         raise ValueError("one output per filter")
     n = filters[0].n if count else 0
     fs = (_F * max(count, 1))(*[f.ptr for f in filters])
     outs = (_vp * max(count, 1))(*[_addr(o) for o in d_outs])
-    name = f"savgol_apply_{'valid_' if valid else ''}multi_batch_f32"
-    rc = getattr(lib(), name)(fs, count, _addr(d_in), outs, channels, length, length if in_ld is None else in_ld,
-                              (length - 2 * n if valid else length) if out_ld is None else out_ld, flags, _stream(stream))
+    in_ld = length if in_ld is None else in_ld
+    out_ld = (length - 2 * n if valid else length) if out_ld is None else out_ld
+    if dtype in ("f16", "bf16"):
+        name = f"savgol_apply_{'valid_' if valid else ''}multi_batch_h16"
+        rc = getattr(lib(), name)(fs, count, _addr(d_in), _STORAGE[dtype], outs, _STORAGE[dtype if out_dtype is None else out_dtype], channels, length, in_ld, out_ld,
+                                  flags, _stream(stream))
+    else:
+        assert dtype == "f32" and out_dtype in (None, "f32"), "the multi-output call serves f32, f16 and bf16 rows; out_dtype belongs to the 16-bit storage types"
+        name = f"savgol_apply_{'valid_' if valid else ''}multi_batch_f32"
+        rc = getattr(lib(), name)(fs, count, _addr(d_in), outs, channels, length, in_ld, out_ld, flags, _stream(stream))
     if rc != 0:
         raise RuntimeError(f"{name} returned {rc}: {last_error()}")
 
 
-def apply_multi_tensor(filters, x, valid=False, flags=0, stream=None):
-    """x: contiguous 2-D float32 torch tensor [channels, length] on the GPU; returns one tensor per filter (same order)."""
+def apply_multi_tensor(filters, x, valid=False, flags=0, stream=None, out_dtype=None):
+    """x: contiguous 2-D float32, float16 or bfloat16 torch tensor [channels, length] on the GPU; returns one tensor per filter (same order).
+    out_dtype (float16 / bfloat16 input only): None = the input's type, or torch.float32."""
     import torch
-    assert x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32
+    names = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
+    if x.dtype not in names:
+        raise TypeError(f"apply_multi_tensor serves float32, float16 and bfloat16 tensors, not {x.dtype}")
+    dtype = names[x.dtype]
+    if out_dtype is not None and out_dtype != x.dtype and not (dtype in ("f16", "bf16") and out_dtype == torch.float32):
+        raise TypeError(f"apply_multi_tensor: {x.dtype} -> {out_dtype} is not served")
+    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
     ch, length = x.shape
     out_len = length - 2 * filters[0].n if valid else length
-    ys = [torch.empty((ch, out_len), dtype=x.dtype, device=x.device) for _ in filters]
-    apply_multi_batch(filters, x, ys, ch, length, length, out_len, flags=flags, valid=valid, stream=stream)
+    ys = [torch.empty((ch, out_len), dtype=x.dtype if out_dtype is None else out_dtype, device=x.device) for _ in filters]
+    apply_multi_batch(filters, x, ys, ch, length, length, out_len, flags=flags, valid=valid, stream=stream, dtype=dtype,
+                      out_dtype=None if out_dtype is None else names[out_dtype])
     return ys
 
 

@@ -16,6 +16,7 @@
 
 #include "sg_k1d_host.hpp"
 #include "sg_k1d_h16_host.hpp"
+#include "sg_k1d_multi_h16_host.hpp"
 #include "sg_runtime.hpp"
 
 using sg::DeviceCtx;
@@ -193,7 +194,7 @@ constexpr size_t LAUNCH_MAX_LENGTH = (size_t)1 << 30;
 // ------------------------------------------------------------------------------------------------
 // The decisions every device route shares, each stated here and nowhere else: the argument checks, what a call stores where
 // (CallShape), what one output adds to it (OutputPart), which kernel family and tile width a call takes, how a batch is cut
-// into launches.  enqueue_multi and enqueue_h16 promise the bits of enqueue_batch<float>: they hold because all three ask these.
+// into launches.  enqueue_multi, enqueue_h16 and enqueue_multi_h16 promise the bits of enqueue_batch<float>: they hold because all four ask these.
 // ------------------------------------------------------------------------------------------------
 
 // The argument checks of a batch call, in this order.  `too_long`: the refusal text (who, length) of a route that does not serve
@@ -587,6 +588,59 @@ int enqueue_long(const char *who, const SavgolFilter *f, const T *d_in, T *d_out
     return ok ? 0 : -1;
 }
 
+// The entries of a multi-output call's two arrays: none NULL, every filter well formed, all of filters[0]'s half_window and boundary
+template <typename P>
+bool multi_filters_match(const char *who, const SavgolFilter *const *filters, P *const *d_outs, int count)
+{
+    for (int k = 0; k < count; ++k) {
+        if (!filters[k] || !d_outs[k]) { sg_set_error("%s: NULL pointer (filters[%d] / d_outs[%d])", who, k, k); return false; }
+        if (!filter_sane(filters[k], who)) return false;
+    }
+    const SavgolFilter *f0 = filters[0];
+    const int n = f0->config.half_window;
+    for (int k = 1; k < count; ++k) {
+        if (filters[k]->config.half_window != n) {
+            sg_set_error("%s: filters[%d] has half_window %d, filters[0] %d (all filters need the same half_window)", who, k, (int)filters[k]->config.half_window, n);
+            return false;
+        }
+        if (filters[k]->config.boundary != f0->config.boundary) {
+            sg_set_error("%s: filters[%d] has boundary %d, filters[0] %d (all filters need the same boundary)", who, k, (int)filters[k]->config.boundary,
+                         (int)f0->config.boundary);
+            return false;
+        }
+    }
+    return true;
+}
+
+// The outputs of ONE fused launch into its job and taps: filters[idx[0 .. K)], the smoothing outputs first (they read the raw slab, sg_k1d_multi.hpp),
+// each with its OutputPart and its edge rows.  out_elem: bytes of an output element (alignment is counted in the buffer's own type).  false: no plan.
+template <typename P>
+bool multi_launch_outputs(DeviceCtx *ctx, sg::JobMulti1D &jm, sg::TapsMulti &taps, const SavgolFilter *const *filters, P *const *d_outs, const int *idx, int K,
+                          const CallShape &shape, unsigned flags, size_t out_ld, size_t out_elem)
+{
+    constexpr unsigned E = 4;
+    int order[sg::MULTI_MAX_K], no = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < K; ++i)
+            if ((filters[idx[i]]->config.derivative >= 1) == (pass == 1)) order[no++] = idx[i];
+    memset(&taps, 0, sizeof(taps));
+    jm.nraw = 0;
+    for (int j = 0; j < K; ++j) {
+        const SavgolFilter *f = filters[order[j]];
+        const FilterPlan *plan = plan_get(ctx, f, shape.want_edges ? NEED_EDGES : 0u);
+        if (!plan) return false;
+        const OutputPart o = output_part(f, shape, flags, true, rows_vector_aligned(d_outs[order[j]], out_ld, out_elem, E, shape.out_shift));
+        taps.t[j] = plan->taps32;
+        jm.out[j] = d_outs[order[j]];
+        jm.edges[j] = shape.want_edges ? plan->d_edges : nullptr;
+        jm.dt_inv[j] = o.dt_inv;
+        jm.centre_sum[j] = o.centre_sum;
+        jm.flags[j] = o.flags;
+        if (!(o.flags & sg::JOB_CENTRE)) ++jm.nraw;
+    }
+    return true;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Several filters of one half window and one boundary mode on the same batch (savgol_apply[_valid]_multi_batch_f32): one read of the input for
 // 2 or 3 outputs (sg1d_multi_kernel, sg_k1d_multi.hpp).  Output k is the single call's with SAVGOL_BATCH_PLAIN_SUMMATION, bit for bit: the fused
@@ -601,23 +655,9 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
 {
     if (!filters || !d_outs || !d_in) { sg_set_error("%s: NULL pointer", who); return -1; }
     if (count < 1 || count > SAVGOL_MULTI_MAX_FILTERS) { sg_set_error("%s: count %d outside 1..%d", who, count, SAVGOL_MULTI_MAX_FILTERS); return -1; }
-    for (int k = 0; k < count; ++k) {
-        if (!filters[k] || !d_outs[k]) { sg_set_error("%s: NULL pointer (filters[%d] / d_outs[%d])", who, k, k); return -1; }
-        if (!filter_sane(filters[k], who)) return -1;
-    }
+    if (!multi_filters_match(who, filters, d_outs, count)) return -1;
     const SavgolFilter *f0 = filters[0];
     const int n = f0->config.half_window;
-    for (int k = 1; k < count; ++k) {
-        if (filters[k]->config.half_window != n) {
-            sg_set_error("%s: filters[%d] has half_window %d, filters[0] %d (all filters need the same half_window)", who, k, (int)filters[k]->config.half_window, n);
-            return -1;
-        }
-        if (filters[k]->config.boundary != f0->config.boundary) {
-            sg_set_error("%s: filters[%d] has boundary %d, filters[0] %d (all filters need the same boundary)", who, k, (int)filters[k]->config.boundary,
-                         (int)f0->config.boundary);
-            return -1;
-        }
-    }
     if (!check_rows(who, f0, d_in, d_outs[0], length, in_ld, out_ld, variant)) return -1;
     if (channels == 0) return 0;
     const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
@@ -658,29 +698,11 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
     job_init(jm.base, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, sizeof(float), E));
     const unsigned tpc = jm.base.tiles_per_channel;
 
-    // launches of 3, 2 or 2 + 2 outputs; within a launch the smoothing outputs first (they read the raw slab, sg_k1d_multi.hpp)
+    // launches of 3, 2 or 2 + 2 outputs
     for (int g0 = 0; g0 < nf;) {
         const int K = (nf - g0 == 4) ? 2 : (nf - g0);
-        int order[sg::MULTI_MAX_K], no = 0;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int i = g0; i < g0 + K; ++i)
-                if ((filters[fused[i]]->config.derivative >= 1) == (pass == 1)) order[no++] = fused[i];
         sg::TapsMulti taps;
-        memset(&taps, 0, sizeof(taps));
-        jm.nraw = 0;
-        for (int j = 0; j < K; ++j) {
-            const SavgolFilter *f = filters[order[j]];
-            const FilterPlan *plan = plan_get(ctx, f, shape.want_edges ? NEED_EDGES : 0u);
-            if (!plan) return -1;
-            const OutputPart o = output_part(f, shape, flags, true, rows_vector_aligned(d_outs[order[j]], out_ld, sizeof(float), E, shape.out_shift));
-            taps.t[j] = plan->taps32;
-            jm.out[j] = d_outs[order[j]];
-            jm.edges[j] = shape.want_edges ? plan->d_edges : nullptr;
-            jm.dt_inv[j] = o.dt_inv;
-            jm.centre_sum[j] = o.centre_sum;
-            jm.flags[j] = o.flags;
-            if (!(o.flags & sg::JOB_CENTRE)) ++jm.nraw;
-        }
+        if (!multi_launch_outputs(ctx, jm, taps, filters, d_outs, fused + g0, K, shape, flags, out_ld, sizeof(float))) return -1;
         // the edge items of every output counted
         for (ChannelGroups g{channels, launch_max_channels(tpc, 2 * (unsigned)K)}; g.next();) {
             sg::JobMulti1D j = jm;
@@ -706,26 +728,36 @@ const char *storage_name(int t)
     return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown";
 }
 
-int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
-                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+// check_rows' refusal text of both 16-bit routes (who, length)
+constexpr const char *H16_TOO_LONG = "%s: channels longer than 2^30 samples (%zu) are not served on 16-bit storage";
+
+// what both 16-bit routes refuse first, in this order: the flags they do not serve, then the storage pair
+bool h16_call_served(const char *who, unsigned flags, int in_type, int out_type)
 {
     if (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) {
         sg_set_error("%s: SAVGOL_BATCH_REFERENCE_SUMMATION is not served on 16-bit storage (the reference has no 16-bit form to be identical to)", who);
-        return -1;
+        return false;
     }
-    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on 16-bit storage (the call runs the narrow tile)", who); return -1; }
+    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on 16-bit storage (the call runs the narrow tile)", who); return false; }
     if (flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64)) {
         sg_set_error("%s: flags 0x%x belong to other calls (BOUNDARY_AWARE: strided calls, MOMENT_F64: fp64 calls)", who, flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64));
-        return -1;
+        return false;
     }
-    if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return -1; }
+    if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return false; }
     const bool in16 = in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16;
     if (!in16 || !(out_type == in_type || out_type == SAVGOL_HIP_F32)) {
         sg_set_error("%s: storage pair %s -> %s (%d -> %d) is not served (f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32; f32 -> f32 is savgol_apply_batch_f32)", who,
                      storage_name(in_type), storage_name(out_type), in_type, out_type);
-        return -1;
+        return false;
     }
-    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, "%s: channels longer than 2^30 samples (%zu) are not served on 16-bit storage")) return -1;
+    return true;
+}
+
+int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
+                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+{
+    if (!h16_call_served(who, flags, in_type, out_type)) return -1;
+    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, H16_TOO_LONG)) return -1;
     if (channels == 0) return 0;
     const int n = f->config.half_window;
     const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
@@ -760,6 +792,74 @@ int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in
         const unsigned blocks = grid_blocks(job.total_tiles + job.edge_items);
         const int rc = d_moment ? MOMENT_H16[terms_slot(plan->moment_terms)](n, &jh, d_moment, blocks, st) : sg::launch_h16(n, jh, plan->taps32, blocks, st);
         if (rc != 0) return -1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Several filters on one read of 16-bit rows (savgol_apply[_valid]_multi_batch_h16): enqueue_multi's job built with enqueue_h16's storage rules, on
+// sg1d_multi_h16_kernel (sg_k1d_multi_h16.hpp).  The narrow tile and the plain summation are implied, so every output fuses: 2 or 3 outputs are one
+// launch, 4 are two launches of two, 1 is the 16-bit single call with SAVGOL_BATCH_PLAIN_SUMMATION.  The checks, in this order (the first fault wins):
+//   1. flags, as enqueue_h16: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the storage pair;
+//   3. NULL filters / d_outs / d_in;   4. count;   5. a NULL or malformed entry, k ascending;   6. half_window, then boundary, of filters[k] against
+//   filters[0], k ascending;   7. check_rows: length < window, channels beyond 2^30 samples, pitches;   (zero channels: 0, nothing enqueued)
+//   8. shared bytes, k ascending: d_outs[k] against d_in, then against d_outs[j], j < k;   9. the kernel objects are linked;   10. a usable device.
+// ------------------------------------------------------------------------------------------------
+int enqueue_multi_h16(const char *who, const SavgolFilter *const *filters, int count, const void *d_in, int in_type, void *const *d_outs, int out_type,
+                      size_t channels, size_t length, size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+{
+    if (!h16_call_served(who, flags, in_type, out_type)) return -1;
+    if (!filters || !d_outs || !d_in) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (count < 1 || count > SAVGOL_MULTI_MAX_FILTERS) { sg_set_error("%s: count %d outside 1..%d", who, count, SAVGOL_MULTI_MAX_FILTERS); return -1; }
+    if (!multi_filters_match(who, filters, d_outs, count)) return -1;
+    const SavgolFilter *f0 = filters[0];
+    const int n = f0->config.half_window;
+    if (!check_rows(who, f0, d_in, d_outs[0], length, in_ld, out_ld, variant, H16_TOO_LONG)) return -1;
+    if (channels == 0) return 0;
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
+    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
+    for (int k = 0; k < count; ++k) {
+        if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_outs[k], out_ld * ob, out_len * ob, channels)) {
+            sg_set_error("%s: d_outs[%d] overlaps d_in (the multi-output call does not run in place: input and output rows may not share a byte)", who, k);
+            return -1;
+        }
+        for (int j = 0; j < k; ++j)
+            if (rows_overlap_bytes((uintptr_t)d_outs[j], out_ld * ob, out_len * ob, (uintptr_t)d_outs[k], out_ld * ob, out_len * ob, channels)) {
+                sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap", who, j, k);
+                return -1;
+            }
+    }
+    if (count == 1) return enqueue_h16(who, f0, d_in, in_type, d_outs[0], out_type, channels, length, in_ld, out_ld, variant, st, flags | SAVGOL_BATCH_PLAIN_SUMMATION);
+    if (!sg1d_launch_multi_h16) { sg_set_error("%s: the 16-bit multi-output kernels are not part of this build (object not linked)", who); return -1; }
+
+    DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    const CallShape shape = call_shape(f0, variant, length);
+    constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
+    sg::JobMultiH16 jh;
+    memset(&jh, 0, sizeof(jh));
+    sg::JobMulti1D &jm = jh.multi;
+    job_init(jm.base, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
+    jh.in_type = (unsigned)in_type;
+    jh.out_type = (unsigned)out_type;
+    const unsigned tpc = jm.base.tiles_per_channel;
+    const int all[SAVGOL_MULTI_MAX_FILTERS] = {0, 1, 2, 3};
+
+    // launches of 3, 2 or 2 + 2 outputs
+    for (int g0 = 0; g0 < count;) {
+        const int K = (count - g0 == 4) ? 2 : (count - g0);
+        sg::TapsMulti taps;
+        if (!multi_launch_outputs(ctx, jm, taps, filters, d_outs, all + g0, K, shape, flags, out_ld, ob)) return -1;
+        // the edge items of every output counted
+        for (ChannelGroups g{channels, launch_max_channels(tpc, 2 * (unsigned)K)}; g.next();) {
+            sg::JobMultiH16 j = jh;
+            j.multi.base.in = static_cast<const char *>(d_in) + g.c0 * in_ld * ib;
+            for (int o = 0; o < K; ++o) j.multi.out[o] = static_cast<char *>(jm.out[o]) + g.c0 * out_ld * ob;
+            j.multi.base.total_tiles = (unsigned)(g.nc * tpc);
+            j.multi.base.edge_items = shape.want_edges ? (unsigned)(2 * g.nc * (size_t)K) : 0u;
+            if (sg1d_launch_multi_h16(n, K, &j, &taps, grid_blocks(j.multi.base.total_tiles + j.multi.base.edge_items), st) != 0) return -1;
+        }
+        g0 += K;
     }
     return 0;
 }
@@ -1031,6 +1131,20 @@ int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, i
                                  size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
     return enqueue_h16("savgol_apply_valid_batch_h16", filter, d_in, in_type, d_out, out_type, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_multi_batch_h16(const SavgolFilter *const *filters, int count, const void *d_in, int in_type, void *const *d_outs, int out_type, size_t channels,
+                                 size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_multi_h16("savgol_apply_multi_batch_h16", filters, count, d_in, in_type, d_outs, out_type, channels, length, in_ld, out_ld, FULL,
+                             static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_valid_multi_batch_h16(const SavgolFilter *const *filters, int count, const void *d_in, int in_type, void *const *d_outs, int out_type, size_t channels,
+                                       size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_multi_h16("savgol_apply_valid_multi_batch_h16", filters, count, d_in, in_type, d_outs, out_type, channels, length, in_ld, out_ld, VALID,
+                             static_cast<hipStream_t>(stream), flags);
 }
 
 // the entry points without flags: their _ex twin on the process defaults (which only ever hold bits flags_ok accepts)

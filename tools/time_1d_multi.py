@@ -5,7 +5,11 @@ n = 5, m = 3, d = 0 / 1 / 2 (config 1's filter, batched) and n = 16, m = 4, d = 
 their derivative outputs keep the single calls' wide tile and run unfused (include/savgol_hip.h).  Prints ms (median), the speed-up over the single
 calls and the fraction of 8 TB/s at (4 + 4 count) bytes per input sample (the singles' own bytes are count x 8).
    python tools/time_1d_multi.py --libs lib_parent/libsavgol_hip.so lib/libsavgol_hip.so lib_parent/libsavgol_hip.so [--case ...]
-instead A/Bs the FUSED call of several builds on the same buffers, interleaved inside every repetition (tools/ab_libs.py)."""
+instead A/Bs the FUSED call of several builds on the same buffers, interleaved inside every repetition (tools/ab_libs.py).
+   python tools/time_1d_multi.py --h16 bf16 [--out-dtype f32] [--pairs 3] [--txt profiles/multi_h16_1d_time.txt]
+instead times the fused call on 16-bit storage (savgol_apply_multi_batch_h16), n = 4 / 8 / 16 / 32 and count 2 / 3, on `pairs` fresh buffer sets that
+alternate inside every repetition, against: count 16-bit single calls with SAVGOL_BATCH_PLAIN_SUMMATION, the fp32 fused call on the widened data
+(SAVGOL_BATCH_TILE_NARROW), and device copies of the same 16-bit buffers (the input copied into each of the count outputs: 4 count bytes per sample, against the fused call's 2 + 2 count)."""
 import argparse
 import json
 import os
@@ -27,6 +31,10 @@ def main():
     ap.add_argument("--fused-only", action="store_true", help="time only the fused call (counter runs)")
     ap.add_argument("--sweep", action="store_true", help="instead: half windows 4..32, count 2 and 3, against narrow plain-summation single calls")
     ap.add_argument("--libs", nargs="+", default=None, help="A/B the fused call of these builds (list the first one again last for the run's own noise)")
+    ap.add_argument("--h16", default=None, choices=("f16", "bf16"), help="instead: the fused call on 16-bit storage of this type")
+    ap.add_argument("--out-dtype", default=None, choices=("f32",), help="--h16: fp32 outputs instead of the input's type")
+    ap.add_argument("--pairs", type=int, default=3, help="--h16: fresh buffer sets alternating inside every repetition")
+    ap.add_argument("--txt", default=None, help="--h16: also write the table here")
     a = ap.parse_args()
     import torch
     from __graft_entry__ import load_package
@@ -34,6 +42,8 @@ def main():
     ch, L = a.channels, a.length
     if a.libs:
         return ab_libs_main(a, sg, torch)
+    if a.h16:
+        return h16_main(a, sg, torch)
     x = torch.empty((ch, L), dtype=torch.float32, device="cuda")
     sg.synth(x)
     outs = [torch.empty_like(x) for _ in range(3)]
@@ -76,6 +86,71 @@ def main():
                "singles_roofline": round(ch * L * 8 * k / (t_single * 1e-3) / PEAK, 3)}
         rows.append(row)
         print(json.dumps(row), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+
+
+def h16_main(a, sg, torch):
+    ch, L = a.channels, a.length
+    t16 = {"f16": torch.float16, "bf16": torch.bfloat16}[a.h16]
+    tout = torch.float32 if a.out_dtype == "f32" else t16
+    in_b, out_b = 2, 4 if a.out_dtype == "f32" else 2
+    x32 = torch.empty((ch, L), dtype=torch.float32, device="cuda")
+    sg.synth(x32)
+    # `pairs` buffer sets allocated afresh (input + three outputs each); every timed repetition runs once on each set, so the median is over placements too
+    sets = []
+    for _ in range(a.pairs):
+        sets.append((x32.to(t16), [torch.empty((ch, L), dtype=tout, device="cuda") for _ in range(3)]))
+    outs32 = [torch.empty_like(x32) for _ in range(3)]
+
+    def timed(fns):
+        for fn in fns:                                        # warm-up: plans, tables
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.reps):
+            for fn in fns:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    PLAIN, NARROW = sg.SAVGOL_BATCH_PLAIN_SUMMATION, sg.SAVGOL_BATCH_TILE_NARROW
+    head = f"# savgol_apply_multi_batch_h16, {ch} x {L}, {a.h16} -> {a.out_dtype or a.h16}, {a.pairs} buffer sets alternating, {a.reps} repetitions each; ms = median (min .. max)"
+    cols = "# n count | fused16 ms (min .. max) | singles16 ms | fp32 fused ms | count copies ms | singles16 / fused16 | fp32 fused / fused16 | copies / fused16 | fused16 of 8 TB/s at (2 + 2 count) B"
+    lines = [head, cols]
+    print(head + "\n" + cols, flush=True)
+    rows = []
+    for n in (4, 8, 16, 32):
+        for k in (2, 3):
+            label = f"h16 n{n} count{k}"
+            if a.case not in label:
+                continue
+            filters = [sg.Filter(n, 4, d, 1.0, 0) for d in range(k)]
+            fused = timed([lambda x=x, o=o: sg.apply_multi_batch(filters, x, o[:k], ch, L, dtype=a.h16, out_dtype=a.out_dtype) for x, o in sets])
+            single = timed([lambda x=x, o=o: [f.apply_batch(x, y, ch, L, dtype=a.h16, out_dtype=a.out_dtype, flags=PLAIN) for f, y in zip(filters, o)] for x, o in sets])
+            f32 = timed([lambda: sg.apply_multi_batch(filters, x32, outs32[:k], ch, L, flags=NARROW)])
+            if in_b == out_b:
+                copy = timed([lambda x=x, o=o: [y.copy_(x) for y in o[:k]] for x, o in sets])
+            else:
+                copy = (float("nan"),) * 3
+            row = {"case": label, "channels": ch, "length": L, "n": n, "count": k, "in": a.h16, "out": a.out_dtype or a.h16, "fused_ms": round(fused[0], 3),
+                   "fused_min_ms": round(fused[1], 3), "fused_max_ms": round(fused[2], 3), "singles_ms": round(single[0], 3), "fp32_fused_ms": round(f32[0], 3),
+                   "copy_ms": round(copy[0], 3), "speedup_over_singles": round(single[0] / fused[0], 3), "speedup_over_fp32_fused": round(f32[0] / fused[0], 3),
+                   "copy_over_fused": round(copy[0] / fused[0], 3), "fused_roofline": round(ch * L * (in_b + out_b * k) / (fused[0] * 1e-3) / PEAK, 3)}
+            rows.append(row)
+            line = (f"{n:>3} {k} | {fused[0]:7.3f} ({fused[1]:.3f} .. {fused[2]:.3f}) | {single[0]:7.3f} | {f32[0]:7.3f} | {copy[0]:7.3f} | "
+                    f"{single[0] / fused[0]:5.3f} x | {f32[0] / fused[0]:5.3f} x | {copy[0] / fused[0]:5.3f} | {row['fused_roofline']:.3f}")
+            lines.append(line)
+            print(line, flush=True)
+    if a.txt:
+        with open(a.txt, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(rows, fh, indent=1)
