@@ -307,7 +307,9 @@ SavgolStreamBank *savgol_streambank_create(const SavgolConfig *config, size_t st
  *   the fp64 oracle, like the default 1-D batch kernels.  Edge rows (leading burst, _flush, _flush_leading), the resident
  *   tick service and calls of >= 2^31 ticks keep the reference's order.  Half windows <= 16 sum in two interleaved chains in _push
  *   and _push_block alike; above 16 the block push keeps ONE chain per output (its accumulators live in registers) while the
- *   per-tick kernel uses two, so the two calls agree to fp32 rounding there, not bit for bit.  flags 0 == savgol_streambank_create. */
+ *   per-tick kernel uses two, so the two calls agree to fp32 rounding there, not bit for bit.
+ *   _push at half window 1 sums its three taps in ONE chain: the even / odd split would add x0 + x2 before -2 x1 on a second-derivative bank,
+ *   a rounding at twice the streams' offset that the reference's order does not have.  flags 0 == savgol_streambank_create. */
 enum { SAVGOL_STREAMBANK_FMA = 1 };
 SavgolStreamBank *savgol_streambank_create_ex(const SavgolConfig *config, size_t streams, unsigned flags);
 void   savgol_streambank_destroy(SavgolStreamBank *bank);
@@ -325,7 +327,10 @@ int    savgol_streambank_push_full(SavgolStreamBank *bank, const float *d_sample
                                    float *d_out, int max_rows, void *stream);
 /* `ticks` pushes in one launch (ring kept on chip in between): d_samples[t*streams + s],
  * d_out[t*streams + s] is written for every tick t that has a centre output.  Returns the
- * number of ticks that produced output (they are the last ones), -1 on error.                 */
+ * number of ticks that produced output (they are the last ones), -1 on error.
+ * Not in place: when [d_samples, d_samples + ticks*streams) and [d_out, d_out + ticks*streams)
+ * share a byte the call returns -1 ("overlap" in savgol_hip_last_error()) before any launch,
+ * with the bank's counters and ring untouched.  Buffers that touch end to start are fine.     */
 int    savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples, size_t ticks,
                                     float *d_out, void *stream);
 /* trailing / leading edge rows, up to n of them; -1 on bad arguments, 0 if never filled       */

@@ -190,14 +190,21 @@ __global__ __launch_bounds__(256) void sg_bank_tick_n_kernel(float *__restrict__
     float acc = 0.0f;
     if constexpr (FMA) {
         // SAVGOL_STREAMBANK_FMA: fused multiply-adds on two chains (even taps, odd taps), as the block-push kernel's fast form
-        float odd = __fmul_rn(taps.w[1], v[1]);
-        acc = __fmul_rn(taps.w[0], v[0]);
+        if constexpr (N == 1) {
+            // Three taps: the odd chain would hold one tap and hide nothing, and "even taps first" adds x0 + x2 before -2 x1 -- on a second-derivative bank
+            // (taps 1, -2, 1) whose streams ride on an offset that is a rounding at twice the offset, 1.9e-5 of the outputs at an offset of 1000, where
+            // the reference's own order is exact (tests/test_gpu_stream_seams.py).  One chain in tap order: every partial sum stays small.
+            acc = __fmaf_rn(taps.w[2], v[2], __fmaf_rn(taps.w[1], v[1], __fmul_rn(taps.w[0], v[0])));
+        } else {
+            float odd = __fmul_rn(taps.w[1], v[1]);
+            acc = __fmul_rn(taps.w[0], v[0]);
 #pragma unroll
-        for (int i = 2; i < WS; ++i) {
-            if (i & 1) odd = __fmaf_rn(taps.w[i], v[i], odd);
-            else       acc = __fmaf_rn(taps.w[i], v[i], acc);
+            for (int i = 2; i < WS; ++i) {
+                if (i & 1) odd = __fmaf_rn(taps.w[i], v[i], odd);
+                else       acc = __fmaf_rn(taps.w[i], v[i], acc);
+            }
+            acc = __fadd_rn(acc, odd);
         }
-        acc = __fadd_rn(acc, odd);
     } else {
 #pragma unroll
         for (int i = 0; i < WS; ++i) acc = __fadd_rn(acc, __fmul_rn(taps.w[i], v[i]));
@@ -660,6 +667,16 @@ int savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples,
     if (!bank || !d_samples || !d_out) { sg_set_error("savgol_streambank_push_block: NULL pointer"); return -1; }
     if (!sg::bank_on_current_device(bank, "savgol_streambank_push_block")) return -1;
     if (ticks == 0) return 0;
+    {
+        // the block push does not run in place: tiles read halo rows other tiles have already written, and sg_bank_store_tail_kernel would copy
+        // outputs into the ring.  Refused before any launch, counters and ring untouched, like every other device entry point.
+        const unsigned long long bytes = (unsigned long long)ticks * bank->streams * sizeof(float);
+        const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples), out0 = reinterpret_cast<uintptr_t>(d_out);
+        if (in0 < out0 + bytes && out0 < in0 + bytes) {
+            sg_set_error("savgol_streambank_push_block: d_samples and d_out overlap (the block push does not run in place: the two ranges of ticks x streams floats may not share a byte)");
+            return -1;
+        }
+    }
     const int ws = bank->filter->window_size;
     hipStream_t st = static_cast<hipStream_t>(stream);
     sg::DeviceCtx *ctx = sg::ctx_get();

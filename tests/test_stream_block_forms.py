@@ -4,7 +4,9 @@ bands / group / total / grid, the walk's band count -- and the output is compare
 was written from the rules as they stood spread over five places in sg_stream_roll.hip, sg_stream_roll.hpp and sg_stream_dma.hip, not by this program.
 The shapes sit on every seam: half windows 5|6, 10|11, 11|12 (tile shapes of the fused bank), 12|13 (register tiles), 16|17, 19|20 (bit-exact bank),
 20|21 (block moments); streams 127 ... 66 560; 31|32 and 63|64 ticks; aligned and misaligned rows; centred banks with 2 and 3 moment terms; the two
-environment switches; and the three cases the band search's own comment gives.  No GPU needed."""
+environment switches; and the three cases the band search's own comment gives.  The same mock accounts for the GPU seam matrix of
+tests/stream_seams.py (test_seam_matrix_stays_on_its_seams), whose numpy restatement of the reference's order is pinned to the oracle here too.  No GPU needed."""
+import collections
 import os
 import subprocess
 
@@ -73,6 +75,80 @@ def test_block_forms_match_the_golden_line_by_line(lines):
     for got, exp in bad[:5]:
         print(f"golden: {exp}\nnow:    {got}")
     assert not bad, f"{len(bad)} of {len(want)} lines differ from tests/golden/stream_block_forms.txt"
+
+
+@pytest.mark.parametrize("n,m,d,dt", [(1, 0, 0, 1.0), (5, 3, 0, 1.0), (16, 2, 1, 1e-3), (20, 2, 2, 0.5), (32, 4, 2, 0.5), (12, 1, 1, 2.0)])
+def test_seam_matrix_restatement_equals_the_oracle(sgo, n, m, d, dt):
+    """the CPU references of tests/stream_seams.py (centre rows and both flushes in the reference's order) against sgo.Stream, bit for bit"""
+    from tests import stream_seams as seams
+    seams.self_check(n, m, d, dt)
+
+
+def test_seam_matrix_stays_on_its_seams(sg, sgo):
+    """CPU accounting of the GPU seam matrix (tests/stream_seams.py, run by tests/test_gpu_stream_seams.py): every block call of the case list goes through
+    the mock above, unchanged -- n, fma, streams, ticks, the OR of the pointer offsets' low bits, centre (the dispatcher's rule on the oracle's taps), terms
+    (savgol_hip_stream_moment_table), the switches.  For every (n, fma): every form block_form can return for that pair -- found by probing the mock on a
+    grid of shapes -- is taken by at least one call, also under each switch as the child processes run it; every call takes the family the list labels it
+    with; the shapes meant to have a partial last group and an empty tail of the tile order have them; the walk's long calls take two and three bands; the
+    oracle's cost stays inside the budget.  A dispatch rule that moves fails here before the matrix slides off its seams."""
+    from tests import stream_seams as seams
+    family = {"MOMENT_TILES": "TILES", "DMA_TILES": "TILES", "REGISTER_TILES": "REGISTER_TILES", "WALK": "WALK"}
+    probes = [(streams, ticks, mis, centre, terms) for streams in (128, 260, 777) for ticks in (31, 4096) for mis in (0, 4) for centre in (0, 1) for terms in (0, 1, 2, 3)]
+    # (half windows, banks, switches, what select() is given) of the in-process runs and of the child processes that run block pushes, from their own arguments
+    runs = [(seams.HALF_WINDOWS, (0, 1), (1, 1), None, None, False)]
+    for switch, (argv, _) in seams.CHILDREN.items():
+        args = seams.parser().parse_args(argv)
+        if args.n:
+            runs.append((args.n, args.banks, (int(switch != "SAVGOL_HIP_STREAM_DMA"), int(switch != "SAVGOL_HIP_STREAM_MOMENT")), args.filters, args.streams, args.big))
+    assert len(runs) == 3
+    totals = collections.Counter()
+    for half_windows, banks, (dma, mom), filters, streams, big in runs:
+        for n in half_windows:
+            for fma in banks:
+                todo = seams.select(n, fma, filters, streams, big)
+                assert seams.cost(todo) < seams.COST_LIMIT, (n, fma, seams.cost(todo))
+                calls = [(c, t0, ticks, mis) for c in todo for t0, ticks, mis in seams.block_calls(c)]
+                geo = seams.mock_geometry([seams.mock_fields(sg, c, ticks, mis, dma, mom) for c, t0, ticks, mis in calls])
+                possible = {g["form"] for g in seams.mock_geometry([(n, fma, s, t, mis, centre, terms, dma, mom, 2048)
+                                                                     for s, t, mis, centre, terms in probes if fma or not centre])}
+                taken = collections.Counter(g["form"] for g in geo)
+                assert set(taken) == possible, (n, fma, dma, mom, dict(taken), possible)
+                for (c, t0, ticks, mis), g in zip(calls, geo):
+                    assert family[g["form"]] == seams.expect(n, fma, c.streams, mis, ticks, dma), (c, t0, ticks, g["line"])
+                    assert c.streams <= 10000 or ticks <= 100, c
+                    tiles = g["form"] != "WALK"
+                    if c.name == "65 register strips":
+                        assert g["form"] == "REGISTER_TILES", (c, g["line"])
+                    if tiles:
+                        groups = (g["strips"] + g["group"] - 1) // g["group"]
+                        assert g["grid"] > 0
+                    if tiles and (c.name == "129 strips" or (c.name == "65 register strips") or (c.name.endswith("17 strips") and g["form"] == "MOMENT_TILES")):
+                        assert groups >= 2 and g["total"] > g["strips"] * g["bands"], (c, g["line"])     # a narrower last group, an empty tail of the tile order
+                        totals["partial " + g["form"]] += 1
+                    if c.name == "many bands" and tiles:
+                        assert g["bands"] >= 5 and ticks % 32, (c, g["line"])
+                    if c.name == "walk":
+                        ws = 2 * n + 1
+                        assert g["form"] == "WALK"
+                        if ticks >= 16 * ws:
+                            assert g["bands"] == ticks // (8 * ws) and (g["bands"] == 2 or ticks % 3), (c, g["line"])     # two bands; three with a shorter last one
+                            totals["walk in bands"] += 1
+                if dma and mom:
+                    # the combinations the large shapes exist for, where the pair has the form at all
+                    by_name = collections.defaultdict(set)
+                    for (c, t0, ticks, mis), g in zip(calls, geo):
+                        by_name[c.name].add(g["form"])
+                    if "MOMENT_TILES" in possible:
+                        assert "MOMENT_TILES" in by_name["17 strips"] and "MOMENT_TILES" in by_name["129 strips"], (n, fma, dict(by_name))
+                    if "DMA_TILES" in possible:
+                        assert "DMA_TILES" in by_name["129 strips"] and "DMA_TILES" in by_name["whole strips"], (n, fma, dict(by_name))
+                    if "REGISTER_TILES" in possible:
+                        assert "REGISTER_TILES" in by_name["65 register strips"] and "REGISTER_TILES" in by_name["quads"] and "REGISTER_TILES" in by_name["hand-over A"]
+                totals["cases"] += len(todo); totals["block calls"] += len(calls)
+                for form, count in taken.items():
+                    totals[form] += count
+    print(dict(totals))
+    assert totals["partial MOMENT_TILES"] and totals["partial DMA_TILES"] and totals["partial REGISTER_TILES"] and totals["walk in bands"]
 
 
 def test_band_search_reproduces_the_cases_of_its_comment(lines):
