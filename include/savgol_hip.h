@@ -21,6 +21,8 @@
  *     otherwise (reference summation order, unaligned or overlapping fields) launches plus a stream-ordered allocation /
  *     free pair for its two dense frames, from the library's own retained memory pool (no shared scratch, no lock, no
  *     synchronise); savgol2d_apply_rowband_f32 and channels longer than 2^30 samples use the same pool for their scratch;
+ *   - savgol_streambank_push_block_h16: launches plus ONE stream-ordered allocation / free pair from the same pool (the fp32 frames of its head, or
+ *     of the staged route's chunk); capturable after one warm-up call like savgol_streambank_push_block;
  *   - savgol_streambank_save/_load, savgol_hip_synchronize and every host-pointer drop-in call of savgolFilter.h /
  *     savgol_stream.h / savgol2d.h: synchronous by nature (they return host data).
  * Short host-pointer calls (savgol_apply / _valid / _strided on <= 4096 samples and <= 64 K multiply-adds, every savgol_stream_* call
@@ -249,8 +251,8 @@ int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int c
  * that share a byte (in place included: a 16-bit row cannot hold its fp32 halo stash; use separate buffers).
  * Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for 16-bit rows, 16 for fp32 output) move as vectors; any
  * other base or pitch is served element by element.  Like the single calls it only enqueues (after one warm-up call with the same filter), so it
- * can be captured into a graph.  Several filters on one read of 16-bit rows: savgol_apply[_valid]_multi_batch_h16 below.  Not served in 16 bit: the strided, stream-bank and 2-D
- * paths, int16 samples, fp32 -> 16-bit pairs. */
+ * can be captured into a graph.  Several filters on one read of 16-bit rows: savgol_apply[_valid]_multi_batch_h16 below.  Not served in 16 bit: the strided and 2-D
+ * paths, int16 samples, fp32 -> 16-bit pairs.  The stream bank's block push on 16-bit rows: savgol_streambank_push_block_h16 below. */
 enum { SAVGOL_HIP_F32 = 0, SAVGOL_HIP_F16 = 1, SAVGOL_HIP_BF16 = 2 };   /* storage type of a device buffer */
 int savgol_apply_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
                            size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
@@ -333,6 +335,30 @@ int    savgol_streambank_push_full(SavgolStreamBank *bank, const float *d_sample
  * with the bank's counters and ring untouched.  Buffers that touch end to start are fine.     */
 int    savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples, size_t ticks,
                                     float *d_out, void *stream);
+/* The block push on 16-bit STORAGE: fp16 or bf16 samples in, the same type or fp32 out, fp32 arithmetic inside -- 4 bytes per stream-tick
+ * (16 -> 16 bit) or 6 (16 bit -> fp32) instead of the fp32 call's 8, and no widened copy of the samples on the caller's side.
+ * Rows are [tick][stream] with pitch `streams`, in elements of the buffer's own type.  in_type / out_type: SAVGOL_HIP_F16 or SAVGOL_HIP_BF16,
+ * out_type also SAVGOL_HIP_F32; served pairs are savgol_apply_batch_h16's (f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32).
+ * The bank is an ordinary bank (savgol_streambank_create or _create_ex): its ring stays fp32 and holds the samples widened exactly, so this call
+ * mixes freely with _push, _push_full, the fp32 _push_block, both flushes, _save / _load and the tick service.
+ * CONTRACT.  Let the twin be a bank of the same configuration, flags and history that takes savgol_streambank_push_block on the samples widened
+ * exactly to fp32, in 16-byte aligned fp32 buffers.  Every output row equals the twin's row bit for bit, rounded ONCE to nearest even into out_type
+ * (out_type f32: the twin's row itself; NaN positions coincide, NaN payloads are free; overflow into fp16 gives +-Inf).  Rows of ticks without an
+ * output are not written.  Afterwards counters, write position and ring are the twin's: the savgol_streambank_save blobs are equal byte for byte.
+ * The return value is savgol_streambank_push_block's.  None of this depends on the alignment of the 16-bit buffers.
+ * Two routes, chosen before anything is enqueued.  TILES -- streams % 128 == 0, ticks >= 64, both bases 16-byte aligned, and the twin takes its
+ * LDS-DMA tiles: the first 64 ticks (two bands of tiles) are widened into fp32 scratch and go through the fp32 block push, the rest through the
+ * same tiles reading 16-bit rows and storing out_type rows (csrc/sg_stream_dma_h16.hip).  STAGED -- every other call (odd stream counts, unaligned
+ * pointers, fewer than 64 ticks, banks whose fp32 call walks or takes register tiles): the samples are widened into aligned fp32 scratch, pushed
+ * through the fp32 block push and the outputs rounded out; up to 2^24 stream-ticks (128 MiB of scratch) in one piece, longer calls in chunks of
+ * max(64, (2^24 / streams) & ~63) ticks.  ONE EXCEPTION to the contract follows from the chunks: the twin of a chunked call is the same sequence
+ * of fp32 block pushes, chunk by chunk.  That changes bits only for a SAVGOL_STREAMBANK_FMA bank with a derivative filter whose fp32 call walks:
+ * the walk's items are centred on their own extent, which a chunk boundary cuts.
+ * Returns -1 with a text naming the call, before any launch or scratch allocation, counters and ring untouched: a NULL pointer; an unserved
+ * type pair (named); input and output ranges that share a byte (compared byte-wise); more than 2^30 ticks (split the call); the bank on another
+ * device; the tick service running.  ticks == 0 returns 0. */
+int    savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_samples, int in_type, size_t ticks,
+                                        void *d_out, int out_type, void *stream);
 /* trailing / leading edge rows, up to n of them; -1 on bad arguments, 0 if never filled       */
 int    savgol_streambank_flush(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream);
 int    savgol_streambank_flush_leading(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream);

@@ -143,6 +143,7 @@ SIGNATURES = {
     "savgol_streambank_push_wait": (C.c_int, [_vp, _vp, _vp, _vp]),
     "savgol_streambank_push_full": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "savgol_streambank_push_block": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "savgol_streambank_push_block_h16": (C.c_int, [_vp, _vp, C.c_int, _sz, _vp, C.c_int, _vp]),
     "savgol_streambank_flush": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_flush_leading": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_ready": (C.c_bool, [_vp]),
@@ -470,6 +471,14 @@ class StreamBank:
 
     def push_block(self, samples, ticks, out, stream=None):
         return lib().savgol_streambank_push_block(self.ptr, _addr(samples), ticks, _addr(out), _stream(stream))
+
+    def push_block_h16(self, samples, dtype, ticks, out, out_dtype=None, stream=None):
+        """savgol_streambank_push_block_h16: `ticks` rows of fp16 / bf16 samples (dtype "f16" / "bf16"), outputs of out_dtype (None = the same type, or
+        "f32"); the fp32 block push's results on the widened samples, rounded once to nearest even"""
+        out_dtype = dtype if out_dtype is None else out_dtype
+        if dtype not in _STORAGE or out_dtype not in _STORAGE:
+            raise ValueError(f"push_block_h16: dtype {dtype!r} -> {out_dtype!r}")
+        return lib().savgol_streambank_push_block_h16(self.ptr, _addr(samples), _STORAGE[dtype], ticks, _addr(out), _STORAGE[out_dtype], _stream(stream))
 
     def service_start(self, idle_ms=0):
         if lib().savgol_streambank_service_start(self.ptr, idle_ms) != 0:

@@ -19,6 +19,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <immintrin.h>
 
 #include <cstdio>
@@ -29,7 +30,10 @@
 #include "sg_internal.h"
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
+#include "sg_h16.hpp"
 #include "sg_stream.hpp"
+#include "sg_stream_h16.hpp"
+#include "sg_stream_roll.hpp"
 
 extern "C" int sg_small_stream_rows(void *ctx, const float *d_table, const float *ring, int ws, int wp, float dt_inv, int count, const int *row,
                                     const int *backward, float *output);
@@ -160,6 +164,54 @@ __global__ __launch_bounds__(256) void sg_bank_store_tail_kernel(float *__restri
     const size_t first = ticks > (size_t)ws ? ticks - (size_t)ws : 0;
     for (size_t q = first + blockIdx.y; q < ticks; q += gridDim.y)
         ring[(size_t)((wp0 + q) % (size_t)ws) * streams + s] = samples[q * streams + s];
+}
+
+// ---- the block push on 16-bit storage (savgol_streambank_push_block_h16): the two small kernels both routes share, and the ring tail store ----
+// Flat ranges of elements, four per thread: a group of four moves as one vector where the 16-bit side is 8-byte aligned (the fp32 side is library
+// scratch, or checked alike), element by element otherwise -- any base, any length.
+// 16-bit elements [0, count) -> fp32, exactly
+__global__ __launch_bounds__(256) void sg_h16_widen_kernel(const unsigned short *__restrict__ in, float *__restrict__ out, size_t count, int bf)
+{
+    const size_t j = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (j >= count) return;
+    if (j + 4 <= count && ((reinterpret_cast<uintptr_t>(in) & 7u) | (reinterpret_cast<uintptr_t>(out) & 15u)) == 0) {
+        const u32x2 raw = *reinterpret_cast<const u32x2 *>(in + j);
+        const f32x2 a = widen2(raw.x, bf != 0), b = widen2(raw.y, bf != 0);
+        *reinterpret_cast<f32x4 *>(out + j) = f32x4{a.x, a.y, b.x, b.y};
+        return;
+    }
+    for (size_t i = j; i < count && i < j + 4; ++i) out[i] = widen1(in[i], bf != 0);
+}
+// fp32 elements [lo, hi) -> out_type, rounded once to nearest even (fp32: copied); elements outside the range -- rows of ticks without an output -- are not written
+__global__ __launch_bounds__(256) void sg_h16_round_kernel(const float *__restrict__ in, void *__restrict__ out, size_t lo, size_t hi, int out_type)
+{
+    const size_t j = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4 + (lo & ~(size_t)3);
+    if (j >= hi) return;
+    const bool whole = j >= lo && j + 4 <= hi && (reinterpret_cast<uintptr_t>(in) & 15u) == 0;
+    if (out_type == (int)H16_STORE_F32) {
+        float *o = static_cast<float *>(out);
+        if (whole && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) { *reinterpret_cast<f32x4 *>(o + j) = *reinterpret_cast<const f32x4 *>(in + j); return; }
+        for (size_t i = j < lo ? lo : j; i < hi && i < j + 4; ++i) o[i] = in[i];
+        return;
+    }
+    const bool bf = out_type == (int)H16_STORE_BF16;
+    unsigned short *o = static_cast<unsigned short *>(out);
+    if (whole && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(in + j);
+        *reinterpret_cast<u32x2 *>(o + j) = u32x2{narrow2(f32x2{v.x, v.y}, bf), narrow2(f32x2{v.z, v.w}, bf)};
+        return;
+    }
+    for (size_t i = j < lo ? lo : j; i < hi && i < j + 4; ++i) o[i] = narrow1(in[i], bf);
+}
+// sg_bank_store_tail_kernel reading 16-bit samples: the ring stays fp32, holding the samples widened exactly
+__global__ __launch_bounds__(256) void sg_bank_store_tail_h16_kernel(float *__restrict__ ring, const unsigned short *__restrict__ samples,
+                                                                     size_t streams, int ws, int wp0, size_t ticks, int bf)
+{
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= streams) return;
+    const size_t first = ticks > (size_t)ws ? ticks - (size_t)ws : 0;
+    for (size_t q = first + blockIdx.y; q < ticks; q += gridDim.y)
+        ring[(size_t)((wp0 + q) % (size_t)ws) * streams + s] = widen1(samples[q * streams + s], bf != 0);
 }
 
 // One tick with every load in flight at once: half window known at compile time, so the 2n ring rows a stream needs
@@ -662,6 +714,22 @@ int savgol_streambank_push_full(SavgolStreamBank *bank, const float *d_samples, 
     return rows.count;
 }
 
+// a block of `ticks` samples per stream has been enqueued: counters and write position; returns the ticks that produced output (the last ones)
+static int bank_advance(SavgolStreamBank *bank, size_t ticks)
+{
+    const int ws = bank->filter->window_size;
+    const unsigned long long before = bank->received;
+    bank->received += ticks;
+    bank->wp = (int)((bank->wp + ticks) % (size_t)ws);
+    unsigned long long produced = 0;
+    if (bank->received >= (unsigned long long)ws) {
+        const unsigned long long first = (before + 1 >= (unsigned long long)ws) ? before + 1 : (unsigned long long)ws;
+        produced = bank->received - first + 1;
+    }
+    bank->emitted += produced;
+    return (int)produced;
+}
+
 int savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples, size_t ticks, float *d_out, void *stream)
 {
     if (!bank || !d_samples || !d_out) { sg_set_error("savgol_streambank_push_block: NULL pointer"); return -1; }
@@ -698,16 +766,137 @@ int savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples,
         done += part;
     }
     if (!sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block launch")) return -1;
-    const unsigned long long before = bank->received;
-    bank->received += ticks;
-    bank->wp = (int)((bank->wp + ticks) % (size_t)ws);
-    unsigned long long produced = 0;
-    if (bank->received >= (unsigned long long)ws) {
-        const unsigned long long first = (before + 1 >= (unsigned long long)ws) ? before + 1 : (unsigned long long)ws;
-        produced = bank->received - first + 1;
+    return bank_advance(bank, ticks);
+}
+
+// ---- savgol_streambank_push_block_h16 ----
+namespace {
+const char *const kH16Who = "savgol_streambank_push_block_h16";
+const char *h16_type_name(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
+
+void h16_widen(const unsigned short *in, float *out, size_t count, bool bf, hipStream_t st)
+{
+    hipLaunchKernelGGL(sg::sg_h16_widen_kernel, dim3((unsigned)((count + 1023) / 1024)), dim3(256), 0, st, in, out, count, bf ? 1 : 0);
+}
+// rows [first_row, rows) of `in` (fp32, pitch streams) -> the same rows of `out`
+void h16_round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, int out_type, hipStream_t st)
+{
+    const size_t lo = first_row * streams, hi = rows * streams;
+    if (lo >= hi) return;
+    const size_t groups = (hi - (lo & ~(size_t)3) + 3) / 4;
+    hipLaunchKernelGGL(sg::sg_h16_round_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, in, out, lo, hi, out_type);
+}
+
+// The staged route: chunk by chunk, widened into fp32 scratch, the fp32 block push (which keeps ring and counters), rounded out.  Returns the outputs
+// produced, -1 on error (text set).  The rows are those of the caller's buffers from row 0 of `d_samples` / `d_out`.
+int h16_staged(SavgolStreamBank *bank, sg::DeviceCtx *ctx, const unsigned short *d_samples, bool ibf, size_t ticks, void *d_out, int out_type, hipStream_t st)
+{
+    const size_t streams = bank->streams, chunk = sg::h16_staged_chunk(streams, ticks);
+    const size_t frame = (chunk * streams * sizeof(float) + 255) & ~(size_t)255;
+    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, kH16Who));
+    if (!scratch) return -1;
+    float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
+    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    long long produced = 0;
+    int rc = 0;
+    for (size_t done = 0; done < ticks && rc >= 0; done += chunk) {
+        const size_t part = ticks - done < chunk ? ticks - done : chunk;
+        h16_widen(d_samples + done * streams, sin, part * streams, ibf, st);
+        rc = savgol_streambank_push_block(bank, sin, part, sout, st);
+        if (rc < 0) break;
+        h16_round(sout, static_cast<char *>(d_out) + done * streams * out_elem, streams, part - (size_t)rc, part, out_type, st);
+        produced += rc;
     }
-    bank->emitted += produced;
+    const bool freed = sg::scratch_free(scratch, st, kH16Who);
+    if (rc < 0 || !freed) return -1;
+    if (!sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block_h16 launch")) return -1;
     return (int)produced;
+}
+}  // namespace
+
+int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_samples, int in_type, size_t ticks, void *d_out, int out_type, void *stream)
+{
+    if (!bank || !d_samples || !d_out) { sg_set_error("%s: NULL pointer", kH16Who); return -1; }
+    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
+        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", kH16Who,
+                     h16_type_name(in_type), h16_type_name(out_type), in_type, out_type);
+        return -1;
+    }
+    if (!sg::bank_on_current_device(bank, kH16Who)) return -1;          // the tick service running, or the bank on another device
+    if (ticks == 0) return 0;
+    if (ticks > ((size_t)1 << 30)) {
+        sg_set_error("%s: %zu ticks in one call, more than 2^30: split the call", kH16Who, ticks);
+        return -1;
+    }
+    const size_t streams = bank->streams;
+    {
+        // not in place, like the fp32 call; compared byte-wise, the element sizes may differ
+        const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * (out_type == SAVGOL_HIP_F32 ? 4 : 2);
+        const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples), out0 = reinterpret_cast<uintptr_t>(d_out);
+        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
+            sg_set_error("%s: d_samples and d_out overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of outputs may not share a byte)",
+                         kH16Who, in_bytes, out_bytes);
+            return -1;
+        }
+    }
+    sg::DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned short *samples = static_cast<const unsigned short *>(d_samples);
+    const bool ibf = in_type == SAVGOL_HIP_BF16, fma = (bank->flags & SAVGOL_STREAMBANK_FMA) != 0;
+    const int n = bank->filter->config.half_window, ws = bank->filter->window_size;
+    const float *weights = bank->filter->center_weights;
+
+    // the route, decided before anything is enqueued (sg_stream_host.hpp).  Centring and the two switches as sg_bank_roll_launch reads them.
+    double wsum = 0.0, wabs = 0.0;
+    for (int k = 0; k <= 2 * n; ++k) { wsum += (double)weights[k]; wabs += std::fabs((double)weights[k]); }
+    const bool centre = fma && std::fabs(wsum) < 1e-3 * wabs;
+    static const int dma_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }();
+    static const int moment_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
+    const unsigned misaligned = (unsigned)((reinterpret_cast<uintptr_t>(d_samples) | reinterpret_cast<uintptr_t>(d_out)) & 15u);
+    sg::StreamMomentFit fit;
+    const sg::H16Plan plan = sg::block_plan_h16(n, fma, streams, ticks, misaligned, centre, dma_env != 0, moment_env != 0,
+                                                [&] { return sg::stream_moment_fit(n, weights, &fit); });
+    if (plan.route == sg::H16_STAGED) return h16_staged(bank, ctx, samples, ibf, ticks, d_out, out_type, st);
+
+    // ---- the tile route: head (two bands through the fp32 tiles), body (the 16-bit tiles), tail store ----
+    const size_t head = plan.head, frame = head * streams * sizeof(float);                  // streams % 128 == 0: the second frame stays aligned
+    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, kH16Who));
+    if (!scratch) return -1;
+    float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
+    h16_widen(samples, sin, head * streams, ibf, st);
+    if (sg::sg_bank_roll_launch(n, weights, bank->d_ring, sin, sout, streams, bank->wp, bank->received, head, bank->dt_inv, fma ? 1 : 0, ctx->cu_count, st) != 0) {
+        (void)sg::scratch_free(scratch, st, kH16Who);
+        sg_set_error("%s: no kernel for half_window %d", kH16Who, n);
+        return -1;
+    }
+    const size_t silent = bank->received + 1 >= (unsigned long long)ws ? 0 : (size_t)((unsigned long long)ws - 1 - bank->received);      // head ticks without an output (<= 2n <= 64)
+    h16_round(sout, d_out, streams, silent, head, out_type, st);
+    const bool freed = sg::scratch_free(scratch, st, kH16Who);
+    int covered = 0;
+    if (plan.body) {
+        sg::BankJobH16 job;
+        memset(&job, 0, sizeof(job));
+        job.samples = samples; job.out = d_out; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
+        job.dt_inv = bank->dt_inv; job.centre_sum = (float)wsum; job.centre = centre ? 1 : 0;
+        job.in_type = (unsigned)in_type; job.out_type = (unsigned)out_type;
+        if (plan.form == sg::MOMENT_TILES) covered = sg::sg_bank_dma_h16_launch_mom(n, fit, weights, job, plan.geo, plan.grid, st);
+        else covered = (n <= 16 ? sg::sg_bank_dma_h16_launch_lo : sg::sg_bank_dma_h16_launch_hi)(n, fma ? 1 : 0, weights, job, plan.geo, plan.grid, st);
+    }
+    const dim3 tail_grid((unsigned)((streams + 255) / 256), 8);
+    if (covered != 0) {
+        // the runtime refused the body's launch (nothing of the body is enqueued): the head becomes a finished block push of its own -- its newest
+        // samples into the ring, the counters -- and the rest of the call takes the staged route
+        hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, tail_grid, dim3(256), 0, st, bank->d_ring, samples, streams, ws, bank->wp, head, ibf ? 1 : 0);
+        const int first = bank_advance(bank, head);
+        const int rest = h16_staged(bank, ctx, samples + head * streams, ibf, plan.body,
+                                    static_cast<char *>(d_out) + head * streams * (out_type == SAVGOL_HIP_F32 ? 4 : 2), out_type, st);
+        return rest < 0 || !freed ? -1 : first + rest;
+    }
+    // the newest min(ticks, 2n + 1) samples, widened, into the ring; the counters once
+    hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, tail_grid, dim3(256), 0, st, bank->d_ring, samples, streams, ws, bank->wp, ticks, ibf ? 1 : 0);
+    if (!freed || !sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block_h16 launch")) return -1;
+    return bank_advance(bank, ticks);
 }
 
 static int bank_edge_rows(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream, bool leading, const char *who)

@@ -25,6 +25,7 @@
 #include "sg_internal.h"
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
+#include "sg_stream_dma.hpp"
 #include "sg_stream_roll.hpp"
 
 namespace sg {
@@ -32,66 +33,6 @@ namespace sg {
 #ifndef SG_DMA_MAX_N
 #define SG_DMA_MAX_N 32
 #endif
-
-// output ticks per tile TR: the slab is TR + 2n rows of 512 bytes, the accumulators 2 (reference order) or 4 (two FMA chains) VGPRs per tick
-template <int N, int TR_> struct DmaShape {
-    static constexpr int TR = TR_;
-    static constexpr int ROWS = TR + 2 * N, NI = ROWS / 2, RB = 512, SLAB = ROWS * RB;
-    static_assert(TR % 2 == 0, "a DMA instruction moves two rows");
-};
-
-template <int K> __device__ __forceinline__ void wait_vm()
-{
-    static_assert(K >= 0 && K < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K) : "memory");
-}
-
-// one 1 KiB LDS-DMA: lane l's 16 bytes land at lds_dst + 16 l.  Inline asm (the compiler then neither counts it nor drains it at the
-// first LDS read: the waits are counted by hand below); M0 is the compiler's, so it is saved and restored in the same statement.
-__device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-// vmcnt bookkeeping, all at compile time.  The wave's vector-memory queue, in issue order: the DP DMAs of the prologue, then per step j
-// (= row pair j): the stores of the outputs that rows 2j, 2j + 1 finish, then DMA j + DP (if that pair exists).
-template <int N, int TR, int DP> struct DmaQueue {
-    static constexpr int NI = (TR + 2 * N) / 2;
-    static constexpr int done(int r) { return r - 2 * N < 0 ? 0 : (r - 2 * N > TR ? TR : r - 2 * N); }     // outputs finished by rows < r = stores issued
-    static constexpr int dmas(int a, int b) { int c = 0; for (int j = a; j < b; ++j) c += (j >= 0 && j + DP < NI) ? 1 : 0; return c; }  // DMAs issued by steps [a, b)
-    // operations younger than DMA p when step g starts (p = g + 1 is the pair step g waits for)
-    static constexpr int younger(int p, int g)
-    {
-        if (p < DP) return (DP - 1 - p) + done(2 * g) + dmas(0, g);                     // a prologue DMA: the rest of the prologue, then every step so far
-        const int born = p - DP;                                                        // issued at the END of step `born`
-        return (done(2 * g) - done(2 * born + 2)) + dmas(born + 1, g);
-    }
-};
-
-// ---- block moments down the tick axis (round 5, profiles/EXPERIMENTS.md R5.9) ----
-// The fused bank's taps are a polynomial in the tap index for the filters streams are made of (config 3: m = 2, d = 1 -- LINEAR taps).  A tile's rows
-// are cut into blocks of 8 ticks (tile-relative rows 8j .. 8j + 7); output m = 8a + p takes the rows of its window that fill whole blocks through the
-// blocks' M moments (M coefficients per block, the same for both streams of the lane) and only the rows before its first / after its last whole block
-// tap by tap: at n = 16, 7 direct taps + 3.25 blocks x M per output on average, plus M operations per input row for the moments -- 17.5 (M = 2)
-// instead of 33 packed multiply-adds per output pair.  Same idea as sg_k1d_momenth.hpp, along the other axis.
-template <int N> struct MomGeom {
-    static constexpr int BK = 8;
-    static constexpr int NOFF = 2 * N - (BK - 1) + 1;                                    // block offsets 8j - m = 0 .. 2N - 7
-    static constexpr int jf(int m) { return m / BK + (m % BK ? 1 : 0); }                 // first / last block that lies wholly inside the window m .. m + 2N
-    static constexpr int jl(int m) { return (m + 2 * N - (BK - 1)) / BK; }
-    static constexpr bool whole(int m, int r) { return r >= m && r <= m + 2 * N && r / BK >= jf(m) && r / BK <= jl(m); }
-    static constexpr bool direct(int m, int r) { return r >= m && r <= m + 2 * N && !whole(m, r); }
-    static_assert(N >= BK / 2, "a window holds at least one whole block");
-};
-// q_0 = 1, q_1(t) = t - 3.5, q_2(t) = (t - 3.5)^2 - 5.25 on t = 0..7 (orthogonal; every value exact in fp32)
-template <int N, int M> struct MomTaps {
-    f32x2 head[4];                                   // w[0 .. 7]        (direct taps before the first whole block: k <= 6)
-    f32x2 tail[4];                                   // w[2N - 7 .. 2N]  (direct taps after the last whole block: k >= 2N - 6)
-    f32x2 c[M][(MomGeom<N>::NOFF + 1) / 2];          // c[s][off]: the block at offset off = 8j - m contributes sum_s c[s][off] * moment_s
-    f32x2 q[M > 1 ? M - 1 : 1][4];                   // q_s(t), s = 1 .. M - 1
-};
 
 template <int N, bool FMA, int TRT, int WPB, int DP, int FCH = 2, int MOM = 0, class TAPS = SRollTaps<N>>
 __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job, const TAPS taps, const TileGeom geo)
@@ -142,73 +83,7 @@ __global__ __launch_bounds__(64 * WPB) void sg_bank_dma_kernel(const BankJob job
     };
     auto feed = [&](auto rc, const f32x2 x) {
         constexpr int r = decltype(rc)::value;
-        constexpr int mlo = r - 2 * N > 0 ? r - 2 * N : 0, mhi = r < TR - 1 ? r : TR - 1;
-        if constexpr (MOM > 0) {
-            typedef MomGeom<N> G;
-            static_assert(N >= 8, "head taps (k <= 6) and tail taps (k >= 2N - 6) must not meet");
-            constexpr int j = r / G::BK, t = r % G::BK;
-            // the block's moments (tap-free: shared by every output that takes this block whole)
-            if constexpr (t == 0) {
-                mom[0] = x;
-                static_for<MOM - 1>([&](auto sc) -> bool { constexpr int sm = decltype(sc)::value; mom[sm + 1] = pk_mul_sgpr<(t & 1)>(taps.q[sm][t >> 1], x); return true; });
-            } else {
-                mom[0] = mom[0] + x;
-                static_for<MOM - 1>([&](auto sc) -> bool { constexpr int sm = decltype(sc)::value; pk_fma_sgpr<(t & 1)>(mom[sm + 1], taps.q[sm][t >> 1], x); return true; });
-            }
-            // rows before an output's first / after its last whole block: tap by tap
-            static_for<mhi - mlo + 1>([&](auto ic) -> bool {
-                constexpr int m = mlo + decltype(ic)::value, k = r - m;
-                if constexpr (G::direct(m, r)) {
-                    constexpr bool is_head = k < G::BK;
-                    constexpr int kk = is_head ? k : k - (2 * N - (G::BK - 1));
-                    static_assert(kk >= 0 && kk < 8, "direct taps sit within 7 of either end of the window");
-                    if constexpr (k == 0) acc[0][m] = pk_mul_sgpr<(kk & 1)>(taps.head[kk >> 1], x);                    // m % 8 != 0: the output's first term
-                    else if constexpr (is_head) pk_fma_sgpr<(kk & 1)>(acc[0][m], taps.head[kk >> 1], x);
-                    else pk_fma_sgpr<(kk & 1)>(acc[0][m], taps.tail[kk >> 1], x);
-                }
-                return true;
-            });
-            // a block is complete: its share of every output that takes it whole
-            if constexpr (t == G::BK - 1) {
-                static_for<mhi - mlo + 1>([&](auto ic) -> bool {
-                    constexpr int m = mlo + decltype(ic)::value;
-                    if constexpr (G::whole(m, r)) {
-                        constexpr int off = G::BK * j - m;
-                        static_assert(off >= 0 && off < G::NOFF, "block offset");
-                        static_for<MOM>([&](auto sc) -> bool {
-                            constexpr int sm = decltype(sc)::value;
-                            if constexpr (sm == 0 && off == 0) acc[0][m] = pk_mul_sgpr<(off & 1)>(taps.c[0][off >> 1], mom[0]);  // m % 8 == 0: the output's first term
-                            else pk_fma_sgpr<(off & 1)>(acc[0][m], taps.c[sm][off >> 1], mom[sm]);
-                            return true;
-                        });
-                    }
-                    return true;
-                });
-            }
-        } else if constexpr (FMA) {
-            static_for<mhi - mlo + 1>([&](auto ic) -> bool {
-                constexpr int m = mlo + decltype(ic)::value, k = r - m;
-                // two chains (even taps, odd taps), one v_pk_fma_f32 per tap: bank_roll_item's fast form, bit for bit -- or ONE chain in the
-                // reference's order (taller tiles fit the registers; each term rounds once where the reference rounds twice)
-                if constexpr (k < CH) acc[k][m] = pk_mul_sgpr<k>(taps.w[0], x);
-                else pk_fma_sgpr<(k & 1)>(acc[(k & 1) % CH][m], taps.w[k >> 1], x);
-                return true;
-            });
-        } else {
-            // the reference's order (src/savgol_stream.c:25-38): sum = 0; sum += w[k] * x[k], k ascending, product and sum rounded separately.
-            // Volatile asm for products and sums alike, each product issued one output ahead of its sum: left to the compiler, all the
-            // products of a row are hoisted in front of the sums and stay live (256 registers and scratch; see bank_accroll_item)
-            f32x2 p = pk_mul_tap<r - mlo>(taps, x);
-            static_for<mhi - mlo + 1>([&](auto ic) -> bool {
-                constexpr int m = mlo + decltype(ic)::value, k = r - m;
-                f32x2 pn = p;
-                if constexpr (m < mhi) pn = pk_mul_tap<k - 1>(taps, x);
-                if constexpr (k == 0) asm volatile("v_pk_add_f32 %0, %1, 0 op_sel_hi:[1,0]" : "=v"(acc[0][m]) : "v"(p));       // 0 + p: a product of -0 sums to +0, as in the reference
-                else                  asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc[0][m]) : "v"(p));
-                p = pn;
-                return true;
-            });
-        }
+#include "sg_stream_dma_feed.hpp"
         if constexpr (r >= 2 * N && r - 2 * N < TR) {                                             // output m = r - 2N has seen its last row
             constexpr int m = r - 2 * N;
             f32x2 a = acc[0][m];

@@ -1,5 +1,6 @@
 // sg_stream_host.hpp -- host-only rules of the stream block push (no device types: included by g++ translation units too): which form a call takes
-// (block_form), the geometry of its tiles or bands, how taps are packed.  tests/mock/stream_block_forms.cpp prints them for a table of call shapes.
+// (block_form), the geometry of its tiles or bands, how taps are packed, the wait counts of the LDS-DMA tiles (DmaQueue) and the routes of the 16-bit
+// call (block_plan_h16).  tests/mock/stream_block_forms.cpp, stream_block_h16.cpp and dma_queue.cpp print them for tables of call shapes.
 #pragma once
 
 #include <cstddef>
@@ -111,6 +112,100 @@ inline BlockForm block_form(int n, bool fma, size_t streams, size_t ticks, unsig
     // 0.403-0.446).  Both forms sit at 0.60-0.69 of the roofline on this 2 GB call, a 0.4 ms launch, whatever the call's length.
     if (first <= REGISTER_TILES && !fma && n <= 12 && tiles_take(streams, 4, misaligned, ticks, 2 * STREAM_TILE_ROWS)) return REGISTER_TILES;
     return WALK;                                             // every half window, every shape (sg_stream_roll.hip)
+}
+
+// ---- LDS-DMA tiles (sg_stream_dma.hpp): compile-time bookkeeping, plain constexpr so that tests/mock/dma_queue.cpp can hold it to a simulated queue ----
+// vmcnt bookkeeping.  A DMA instruction moves RPD rows (2 rows of 512 bytes: fp32 rows; 4 rows of 256 bytes: 16-bit rows); a step consumes the RPD rows of
+// one DMA.  The wave's vector-memory queue, in issue order: the DP DMAs of the prologue, then per step j: the stores of the outputs that rows RPD j ..
+// RPD j + RPD - 1 finish, then DMA j + DP (if it exists).  ROWS = TR + 2N is rounded up to whole DMAs (pad rows finish no output).
+template <int N, int TR, int DP, int RPD = 2> struct DmaQueue {
+    static constexpr int NI = (TR + 2 * N + RPD - 1) / RPD;
+    static constexpr int done(int r) { return r - 2 * N < 0 ? 0 : (r - 2 * N > TR ? TR : r - 2 * N); }     // outputs finished by rows < r = stores issued
+    static constexpr int dmas(int a, int b) { int c = 0; for (int j = a; j < b; ++j) c += (j >= 0 && j + DP < NI) ? 1 : 0; return c; }  // DMAs issued by steps [a, b)
+    // operations younger than DMA p when step g starts (p = g + 1 is the one step g waits for)
+    static constexpr int younger(int p, int g)
+    {
+        if (p < DP) return (DP - 1 - p) + done(RPD * g) + dmas(0, g);                   // a prologue DMA: the rest of the prologue, then every step so far
+        const int born = p - DP;                                                        // issued at the END of step `born`
+        return (done(RPD * g) - done(RPD * born + RPD)) + dmas(born + 1, g);
+    }
+};
+
+// ---- block moments down the tick axis (round 5, profiles/EXPERIMENTS.md R5.9) ----
+// The fused bank's taps are a polynomial in the tap index for the filters streams are made of (config 3: m = 2, d = 1 -- LINEAR taps).  A tile's rows
+// are cut into blocks of 8 ticks (tile-relative rows 8j .. 8j + 7); output m = 8a + p takes the rows of its window that fill whole blocks through the
+// blocks' M moments (M coefficients per block, the same for both streams of the lane) and only the rows before its first / after its last whole block
+// tap by tap: at n = 16, 7 direct taps + 3.25 blocks x M per output on average, plus M operations per input row for the moments -- 17.5 (M = 2)
+// instead of 33 packed multiply-adds per output pair.  Same idea as sg_k1d_momenth.hpp, along the other axis.
+template <int N> struct MomGeom {
+    static constexpr int BK = 8;
+    static constexpr int NOFF = 2 * N - (BK - 1) + 1;                                    // block offsets 8j - m = 0 .. 2N - 7
+    static constexpr int jf(int m) { return m / BK + (m % BK ? 1 : 0); }                 // first / last block that lies wholly inside the window m .. m + 2N
+    static constexpr int jl(int m) { return (m + 2 * N - (BK - 1)) / BK; }
+    static constexpr bool whole(int m, int r) { return r >= m && r <= m + 2 * N && r / BK >= jf(m) && r / BK <= jl(m); }
+    static constexpr bool direct(int m, int r) { return r >= m && r <= m + 2 * N && !whole(m, r); }
+    static_assert(N >= BK / 2, "a window holds at least one whole block");
+};
+
+// ---- the block push on 16-bit rows (savgol_streambank_push_block_h16): which route a call takes, decided before anything is enqueued ----
+// (waves per block, strips per group) of the LDS-DMA tile launchers, by form, half window and bank: launch_bank_dma_shape / launch_bank_dma_mom
+// (sg_stream_dma.hip) and their 16-bit mirrors (sg_stream_dma_h16.hip)
+struct DmaTileShape { int wpb; unsigned group; };
+inline DmaTileShape dma_tile_shape(BlockForm form, int n, bool fma, size_t streams)
+{
+    if (form == MOMENT_TILES) {
+        const unsigned want = (unsigned)(streams / 128 / 4);
+        return DmaTileShape{8, want < 16u ? 16u : (want > 64u ? 64u : want)};
+    }
+    return DmaTileShape{n > 5 && n <= 11 && fma ? 8 : 4, 128u};
+}
+
+// TILES: streams % 128 == 0, ticks >= 64, both 16-bit bases 16-byte aligned (misaligned = their low four bits, or-ed), rows under the descriptor
+// limit, and the fp32 call on aligned buffers (the twin) takes LDS-DMA tiles, block moments or tap by tap, whose tile count 32 bits index.  The call is
+// then a head of STREAM_DMA_MIN_TICKS = 64 ticks = two whole 32-tick bands (widened into fp32 scratch and pushed through the fp32 block push: the twin's
+// own tiles of bands 0 and 1; 2n <= 64, so only the head reads the fp32 ring) and a body of ticks - 64 (the 16-bit tiles: the twin's bands >= 2, `geo`
+// in the twin's tile order with the band index counted from the body's first band).
+// STAGED: every other call: widened into aligned fp32 scratch, the fp32 block push, rounded out -- in one piece up to 2^24 stream-ticks (128 MiB of
+// scratch), else in chunks of max(64, (2^24 / streams) & ~63) ticks.
+enum H16Route { H16_STAGED, H16_TILES };
+constexpr size_t H16_STAGED_MAX = (size_t)1 << 24;
+struct H16Plan {
+    H16Route  route;
+    BlockForm form;                  // TILES: the twin's form (MOMENT_TILES or DMA_TILES)
+    size_t    head, body;            // TILES: 64 and ticks - 64
+    size_t    chunk;                 // STAGED: ticks per fp32 block push (the last chunk takes what is left)
+    TileGeom  geo;                   // TILES with body > 0: the body's tiles ...
+    unsigned  grid;                  // ... and its grid
+    int       wpb;
+};
+inline size_t h16_staged_chunk(size_t streams, size_t ticks)
+{
+    if (ticks <= H16_STAGED_MAX / streams) return ticks;                                // streams * ticks <= 2^24
+    const size_t c = (H16_STAGED_MAX / streams) & ~(size_t)63;
+    return c > 64 ? c : 64;
+}
+template <class Fit>
+inline H16Plan block_plan_h16(int n, bool fma, size_t streams, size_t ticks, unsigned misaligned, bool centre, bool dma_switch, bool moment_switch,
+                              Fit &&moment_terms)
+{
+    H16Plan plan = {};
+    plan.route = H16_STAGED;
+    plan.form = WALK;
+    plan.chunk = h16_staged_chunk(streams, ticks);
+    if (!tiles_take(streams, 128, misaligned, ticks, STREAM_DMA_MIN_TICKS)) return plan;
+    const BlockForm form = block_form(n, fma, streams, ticks, 0u, centre, dma_switch, moment_switch, static_cast<Fit &&>(moment_terms));
+    if (form != MOMENT_TILES && form != DMA_TILES) return plan;
+    const DmaTileShape shape = dma_tile_shape(form, n, fma, streams);
+    TileGeom whole;
+    if (!tile_geom(streams, 128, ticks, 32, shape.group, shape.wpb, &whole)) return plan;   // the twin itself would leave the tiles
+    plan.route = H16_TILES;
+    plan.form = form;
+    plan.head = STREAM_DMA_MIN_TICKS;
+    plan.body = ticks - STREAM_DMA_MIN_TICKS;
+    plan.chunk = 0;
+    plan.wpb = shape.wpb;
+    if (plan.body) plan.grid = tile_geom(streams, 128, plan.body, 32, shape.group, shape.wpb, &plan.geo);
+    return plan;
 }
 
 }  // namespace sg
