@@ -251,8 +251,9 @@ int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int c
  * that share a byte (in place included: a 16-bit row cannot hold its fp32 halo stash; use separate buffers).
  * Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for 16-bit rows, 16 for fp32 output) move as vectors; any
  * other base or pitch is served element by element.  Like the single calls it only enqueues (after one warm-up call with the same filter), so it
- * can be captured into a graph.  Several filters on one read of 16-bit rows: savgol_apply[_valid]_multi_batch_h16 below.  Not served in 16 bit: the strided and 2-D
- * paths, int16 samples, fp32 -> 16-bit pairs.  The stream bank's block push on 16-bit rows: savgol_streambank_push_block_h16 below. */
+ * can be captured into a graph.  Several filters on one read of 16-bit rows: savgol_apply[_valid]_multi_batch_h16 below.  Not served in 16 bit: the strided path,
+ * the 2-D derivative-frame and row-band calls, int16 samples, fp32 -> 16-bit pairs.  The stream bank's block push on 16-bit rows:
+ * savgol_streambank_push_block_h16 below; the 2-D batch call on 16-bit frames: savgol2d_apply_batch_h16 below. */
 enum { SAVGOL_HIP_F32 = 0, SAVGOL_HIP_F16 = 1, SAVGOL_HIP_BF16 = 2 };   /* storage type of a device buffer */
 int savgol_apply_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
                            size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
@@ -401,6 +402,50 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter,
                              const float *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
                              float *d_out, int out_stride, size_t out_image_pitch,
                              size_t images, Savgol2DBoundary boundary, int method, void *stream);
+
+/* The 2-D batch call on 16-bit STORAGE: fp16 or bf16 frames in, the same type or fp32 out, fp32 arithmetic inside -- 4 bytes per pixel (16 -> 16 bit)
+ * or 6 (16 bit -> fp32) instead of the fp32 call's 8, and no widened copy of the frames on the caller's side.
+ * in_type / out_type: SAVGOL_HIP_F16 / _BF16, out_type also SAVGOL_HIP_F32; served pairs are savgol_apply_batch_h16's (f16 -> f16, bf16 -> bf16,
+ * f16 -> f32, bf16 -> f32).  Strides and image pitches count elements of their own buffer's type.
+ * CONTRACT.  The twin is savgol2d_apply_batch_f32 with the same filter, boundary and method on the frames widened exactly to fp32, in buffers with
+ * 16-byte aligned bases, stride = cols rounded up to a multiple of 4 (input and output alike) and image pitch rows x stride.  Every output pixel
+ * equals the twin's pixel bit for bit, rounded ONCE to nearest even into out_type (out_type f32: the twin's pixel itself; NaN positions coincide,
+ * NaN payloads are free; overflow into fp16 gives +-Inf).  Pixels the twin does not write are not written: the VALID border, and every byte between
+ * cols and the stride and between frames.  None of this depends on the alignment of the caller's buffers.  (The twin's alignment is part of the
+ * contract because the fp32 call's additive form re-seeds its rolling column sums at a tile's first row on its tile form and at multiples of U frame
+ * rows on its strip walk, which unaligned fp32 buffers take: the two are not the same bits.)
+ * method: 0, 2 and 3 mean what they mean for the twin.  Method 1 (the dense kernel, whose point is the reference's bits) returns -1: the reference
+ * has no 16-bit form to be identical to -- as savgol_apply_batch_h16 refuses SAVGOL_BATCH_REFERENCE_SUMMATION.
+ * Two routes, chosen by one host rule before anything is enqueued (csrc/sg_2d_h16_host.hpp, frame_plan_h16).  TILES -- the twin launches the rolling
+ * kernel's additive tile form (every smoothing filter of order <= 3 on a square window, half windows 1..16; a rectangular window runs on zero-padded
+ * factors, which are not the additive form, and is staged; not an x-dominant derivative filter,
+ * method 0 or 2), cols % 4 == 0 and cols >= 32, every base, stride and pitch keeps quads naturally aligned (16-bit side: 8-byte base, stride and pitch
+ * multiples of 4; fp32 output: 16-byte base), rows x out_stride x element size and the twin's rows x cols x 4 are under 0x7fffff00, and neither
+ * SAVGOL_HIP_ROLL_TILE nor SAVGOL_HIP_2D_H16_TILES is 0: the same tiles reading 16-bit rows and storing out_type rows (csrc/sg_2d_roll_h16.inc).
+ * STAGED -- every other call runs the twin itself: whole frames (max(1, 2^24 / (rows x stride)) per piece: 64 MiB per side of stream-ordered
+ * scratch unless one frame alone is larger) are widened into aligned fp32 scratch, filtered scratch to scratch and the pixels the twin wrote
+ * rounded out.  Pieces of whole frames do not change bits.
+ * SAVGOL_HIP_2D_H16_TILES is read with getenv at every call (SAVGOL_HIP_ROLL_TILE once per process): a process that rewrites its environment
+ * while other threads are inside the call races with getenv, as with any environment variable; set it before the threads start.
+ * Returns -1 with a text naming the call, before any launch or scratch allocation; the checks run in this order and the first fault wins:
+ *   1. method 1, or a method outside 0..3;   2. an unserved type pair (named);   3. a NULL pointer;   4. an invalid filter struct;
+ *   5. the geometry savgol2d_apply_batch_f32 refuses, with its texts (bad image geometry, image smaller than the window);
+ *   6. input and output stacks that share a byte (compared byte-wise: the element sizes may differ).
+ * One refusal is the twin's own and comes later, on the staged route after its scratch has been allocated and the widen pass enqueued (the scratch is
+ * freed in stream order, d_out is untouched): method 2 or 3 on a filter for which the fp32 call has no separable kernel ("no separable kernel ...").
+ * images == 0 returns 0.  Like its siblings it only enqueues (after one warm-up call with the same filter), so it can be captured into a graph.
+ * Not served in 16 bit: the derivative-frame calls below (a Savgol2DFilter created with deriv_x / deriv_y goes through this call like any other
+ * filter), the row-band calls, int16 / uint16 pixels, fp32 -> 16-bit pairs. */
+int savgol2d_apply_batch_h16(const Savgol2DFilter *filter,
+                             const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
+                             void *d_out, int out_type, int out_stride, size_t out_image_pitch,
+                             size_t images, Savgol2DBoundary boundary, int method, void *stream);
+/* Which route the call above would take for these arguments, decided by the same code and touching no device: 1 = TILES, 0 = STAGED (or no images),
+ * -1 = the call would be refused before any launch (same order, same texts). */
+int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter,
+                                   const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
+                                   const void *d_out, int out_type, int out_stride, size_t out_image_pitch,
+                                   size_t images, Savgol2DBoundary boundary, int method);
 
 /* Derivative frames (arithmetic of savgol2d_gradient / _hessian / _laplacian, src/savgol2d.c:462-618).  The Laplacian
  * writes one frame, with no temporary frame and no add pass.  Outputs may be NULL (skipped), like the reference.

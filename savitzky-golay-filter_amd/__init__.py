@@ -160,6 +160,8 @@ SIGNATURES = {
     "savgol_streambank_load": (C.c_int, [_vp, _vp, _vp]),
     # savgol_hip.h: 2-D batch
     "savgol2d_apply_batch_f32": (C.c_int, [_F2, _vp, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp]),
+    "savgol2d_apply_batch_h16": (C.c_int, [_F2, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp]),
+    "savgol2d_apply_batch_h16_route": (C.c_int, [_F2, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int]),
     "savgol2d_gradient_batch_f32": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, _vp, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int, _vp]),
     "savgol2d_hessian_batch_f32": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, _vp, _vp, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int, _vp]),
     "savgol2d_laplacian_batch_f32": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int, _vp]),
@@ -569,3 +571,18 @@ class Filter2D:
                                             _stream(stream))
         if rc != 0:
             raise RuntimeError(f"savgol2d_apply_batch_f32 returned {rc}: {last_error()}")
+
+    def apply_batch_h16(self, d_in, dtype, d_out, rows, cols, images, out_dtype=None, in_stride=None, out_stride=None, in_pitch=None, out_pitch=None,
+                        boundary=SAVGOL2D_BOUNDARY_VALID, method=0, stream=None):
+        """savgol2d_apply_batch_h16: frames of fp16 / bf16 pixels (dtype "f16" / "bf16"), outputs of out_dtype (None = the same type, or "f32"), the fp32
+        call's arithmetic in between; strides and pitches count elements of their own buffer."""
+        out_dtype = dtype if out_dtype is None else out_dtype
+        if dtype not in ("f16", "bf16") or out_dtype not in (dtype, "f32"):
+            raise ValueError(f"apply_batch_h16: dtype {dtype!r} -> {out_dtype!r}")
+        in_stride = cols if in_stride is None else in_stride
+        out_stride = cols if out_stride is None else out_stride
+        rc = lib().savgol2d_apply_batch_h16(self.ptr, _addr(d_in), _STORAGE[dtype], rows, cols, in_stride,
+                                            rows * in_stride if in_pitch is None else in_pitch, _addr(d_out), _STORAGE[out_dtype], out_stride,
+                                            rows * out_stride if out_pitch is None else out_pitch, images, boundary, method, _stream(stream))
+        if rc != 0:
+            raise RuntimeError(f"savgol2d_apply_batch_h16 returned {rc}: {last_error()}")

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "sg_2d.hpp"
+#include "sg_2d_h16.hpp"
 #include "sg_runtime.hpp"
 
 namespace sg {
@@ -162,59 +163,22 @@ struct CachedFilter {
     ~CachedFilter() { if (owned) savgol2d_destroy(const_cast<Savgol2DFilter *>(f)); }
 };
 
-// Do two frame batches share a byte?  EXACT for strided layouts (round 4 compared the bounding byte ranges only, which refused
-// side-by-side views of one buffer -- in = buf[:, :cols], out = buf[:, cols:], stride 2 cols -- and frames interleaved at a common pitch).
-// Units below are floats relative to `a`; a batch is the set { i*pitch + r*stride + c : i < images, r < rows, c < cols }.
-static bool rows_share(long long a, long long sa, long long b, long long sb, int rows, int cols)
-{
-    // two single frames: merge their row intervals in address order (strides are >= cols, so each frame's rows are sorted and disjoint)
-    int ia = 0, ib = 0;
-    while (ia < rows && ib < rows) {
-        const long long a0 = a + ia * sa, b0 = b + ib * sb;
-        if (a0 < b0 + cols && b0 < a0 + cols) return true;
-        if (a0 + cols <= b0 + cols) ++ia; else ++ib;
-    }
-    return false;
-}
+// Do two fp32 frame batches share a byte?  The exact test for strided layouts lives in sg_2d_h16_host.hpp (plain C++, so that a host program can hold it
+// to its cases), generalised over the element sizes for the call on 16-bit storage; two fp32 stacks get the answers they always got.
 static bool frames_overlap(const float *a, long long a_pitch, int a_stride, const float *b, long long b_pitch, int b_stride, int rows, int cols, size_t images)
 {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    const long long a_frame = (long long)(rows - 1) * a_stride + cols, b_frame = (long long)(rows - 1) * b_stride + cols;      // floats one frame spans
-    const uintptr_t a1 = a0 + sizeof(float) * ((size_t)(images - 1) * (size_t)a_pitch + (size_t)a_frame);
-    const uintptr_t b1 = b0 + sizeof(float) * ((size_t)(images - 1) * (size_t)b_pitch + (size_t)b_frame);
-    if (!(a0 < b1 && b0 < a1)) return false;                                    // bounding ranges apart: the common case
-    // layouts this test does not model exactly are refused as before: bases a fraction of a float apart, frames of one batch running into
-    // each other, negative pitches
-    if ((a0 > b0 ? a0 - b0 : b0 - a0) % sizeof(float) != 0) return true;
-    if (images > 1 && (a_pitch < a_frame || b_pitch < b_frame)) return true;
-    const long long delta = (a0 > b0 ? (long long)((a0 - b0) / sizeof(float)) : -(long long)((b0 - a0) / sizeof(float)));     // a - b in floats
-    if (a_stride == b_stride && (images == 1 || a_pitch == b_pitch)) {
-        // equal strides and pitches: frame i row r col c of `a` meets frame i' row r' col c' of `b` iff
-        // delta = di*pitch + dr*stride + dc with |di| < images, |dr| < rows, |dc| < cols.  Frames and rows of one batch do not run into
-        // each other (pitch >= frame span, stride >= cols), so only two candidates per level can match.
-        const long long s = a_stride, p = images > 1 ? a_pitch : 0;
-        auto fdiv = [](long long x, long long y) { long long q = x / y; if ((x % y != 0) && ((x < 0) != (y < 0))) --q; return q; };
-        for (int ci = 0; ci < (images > 1 ? 2 : 1); ++ci) {
-            const long long di = images > 1 ? fdiv(-delta, p) + ci : 0;
-            if (di <= -(long long)images || di >= (long long)images) continue;
-            const long long rem = -delta - di * p;                                // = dr*stride + dc
-            for (int cr = 0; cr < 2; ++cr) {
-                const long long dr = fdiv(rem, s) + cr;
-                if (dr <= -(long long)rows || dr >= (long long)rows) continue;
-                const long long dc = rem - dr * s;
-                if (dc > -(long long)cols && dc < (long long)cols) return true;
-            }
-        }
+    return frames_overlap(reinterpret_cast<uintptr_t>(a), sizeof(float), a_pitch, a_stride, reinterpret_cast<uintptr_t>(b), sizeof(float), b_pitch, b_stride, rows, cols, images);
+}
+
+// the geometry every 2-D device entry point refuses, with its texts
+static bool geometry_ok(const char *who, int nx, int ny, int rows, int cols, int in_stride, int out_stride, int boundary)
+{
+    if (rows <= 0 || cols <= 0 || in_stride < cols || out_stride < cols) { sg_set_error("%s: bad image geometry", who); return false; }
+    if (boundary == SAVGOL2D_BOUNDARY_VALID && (rows - 2 * ny <= 0 || cols - 2 * nx <= 0)) {
+        sg_set_error("%s: image smaller than the window", who);
         return false;
     }
-    // different strides or pitches: merge the frames' spans in address order, rows of the frame pairs whose spans intersect
-    size_t ia = 0, ib = 0;
-    while (ia < images && ib < images) {
-        const long long fa = delta + (long long)ia * a_pitch, fb = (long long)ib * b_pitch;
-        if (fa < fb + b_frame && fb < fa + a_frame && rows_share(fa, a_stride, fb, b_stride, rows, cols)) return true;
-        if (fa + a_frame <= fb + b_frame) ++ia; else ++ib;
-    }
-    return false;
+    return true;
 }
 
 // What every 2-D device entry point checks once its kernel is known to be valid, and the Job2D it starts from: job.in = d_in, the
@@ -225,11 +189,7 @@ static int make_job(const char *who, int nx, int ny, const float *d_in, float *c
     bool null = !d_in;
     for (int i = 0; i < nout; ++i) null = null || !outs[i];
     if (null) { sg_set_error("%s: NULL pointer", who); return -1; }
-    if (rows <= 0 || cols <= 0 || in_stride < cols || out_stride < cols) { sg_set_error("%s: bad image geometry", who); return -1; }
-    if (boundary == SAVGOL2D_BOUNDARY_VALID && (rows - 2 * ny <= 0 || cols - 2 * nx <= 0)) {
-        sg_set_error("%s: image smaller than the window", who);
-        return -1;
-    }
+    if (!geometry_ok(who, nx, ny, rows, cols, in_stride, out_stride, boundary)) return -1;
     if (images == 0) return 1;
     // No 2-D kernel may run in place: every output reads its neighbours' inputs, tiles of one frame run in any order, and the
     // two-pass form of wide windows re-reads the input after the output has been written.  The reference's loop is no different
@@ -413,17 +373,24 @@ static int enqueue_frame(const char *who, DeviceCtx *ctx, const Job2D &job, int 
     return 0;
 }
 
+static bool filter_ok(const char *who, const Savgol2DFilter *f)
+{
+    const int nx = f->config.half_window_x, ny = f->config.half_window_y;
+    if (nx < 1 || nx > SAVGOL2D_MAX_HALF_WINDOW || ny < 1 || ny > SAVGOL2D_MAX_HALF_WINDOW || !f->weights ||
+        f->window_width != 2 * nx + 1 || f->window_height != 2 * ny + 1) {
+        sg_set_error("%s: filter struct is not a valid Savgol2DFilter", who);
+        return false;
+    }
+    return true;
+}
+
 static int enqueue_2d(const char *who, const Savgol2DFilter *f, const float *d_in, int rows, int cols, int in_stride,
                       long long in_pitch, float *d_out, int out_stride, long long out_pitch, size_t images, int boundary,
                       int method, hipStream_t st)
 {
     if (!f) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (!filter_ok(who, f)) return -1;
     const int nx = f->config.half_window_x, ny = f->config.half_window_y;
-    if (nx < 1 || nx > SAVGOL2D_MAX_HALF_WINDOW || ny < 1 || ny > SAVGOL2D_MAX_HALF_WINDOW || !f->weights ||
-        f->window_width != 2 * nx + 1 || f->window_height != 2 * ny + 1) {
-        sg_set_error("%s: filter struct is not a valid Savgol2DFilter", who);
-        return -1;
-    }
     Job2D job;
     int rc = make_job(who, nx, ny, d_in, &d_out, 1, rows, cols, in_stride, in_pitch, out_stride, out_pitch, images, boundary, job);
     if (rc != 0) return rc > 0 ? 0 : -1;
@@ -545,6 +512,142 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter, const float *d_in, in
 {
     return sg::enqueue_2d("savgol2d_apply_batch_f32", filter, d_in, rows, cols, in_stride, (long long)in_image_pitch, d_out,
                           out_stride, (long long)out_image_pitch, images, (int)boundary, method, static_cast<hipStream_t>(stream));
+}
+
+// ---- the 2-D batch call on 16-bit storage: fp16 / bf16 frames in, the same type or fp32 out, the fp32 call's arithmetic in between ----
+namespace sg {
+
+static const char *const kH16Who2D = "savgol2d_apply_batch_h16";
+static const char *h16_type_name_2d(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
+
+// The staged route: the twin itself.  Whole frames per piece, widened into aligned fp32 scratch, savgol2d_apply_batch_f32's own path (enqueue_2d)
+// scratch to scratch, and the pixels it wrote rounded out.  Pieces of whole frames do not change bits: the additive tile's re-seed phase is the
+// tile, the strip walk's the frame row (launch_roll_kernel), and every other 2-D kernel computes its outputs independently.
+static int h16_staged_2d(DeviceCtx *ctx, const Savgol2DFilter *f, const unsigned short *d_in, bool ibf, int rows, int cols, int in_stride, long long in_pitch,
+                         void *d_out, int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, hipStream_t st)
+{
+    const FrameStageH16 g = frame_stage_h16(rows, cols, images);
+    const size_t side = (g.frames * g.frame * sizeof(float) + 255) & ~(size_t)255;
+    char *scratch = static_cast<char *>(scratch_alloc(ctx, 2 * side, st, kH16Who2D));
+    if (!scratch) return -1;
+    float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + side);
+    const bool valid = boundary == SAVGOL2D_BOUNDARY_VALID;
+    const int nx = f->config.half_window_x, ny = f->config.half_window_y;
+    const int xlo = valid ? nx : 0, xhi = valid ? cols - nx : cols, ylo = valid ? ny : 0, yhi = valid ? rows - ny : rows;
+    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    int rc = 0;
+    for (size_t i0 = 0; i0 < images && rc == 0; i0 += g.frames) {
+        const size_t ni = images - i0 < g.frames ? images - i0 : g.frames;
+        sg2d_h16_widen_frames(d_in + (long long)i0 * in_pitch, in_stride, in_pitch, ibf, sin, rows, cols, ni, st);
+        rc = enqueue_2d(kH16Who2D, f, sin, rows, cols, g.stride, (long long)g.frame, sout, g.stride, (long long)g.frame, ni, boundary, method, st);
+        if (rc != 0) break;
+        sg2d_h16_round_frames(sout, static_cast<char *>(d_out) + i0 * (size_t)out_pitch * out_elem, out_type, out_stride, out_pitch, rows, cols, xlo, xhi, ylo, yhi, ni, st);
+    }
+    const bool freed = scratch_free(scratch, st, kH16Who2D);
+    if (rc != 0 || !freed) return -1;
+    return hip_ok(hipGetLastError(), kH16Who2D) ? 0 : -1;
+}
+
+}  // namespace sg
+
+namespace sg {
+
+// The refusals of the 16-bit call in the header's order, then its route: -1 = refused (text set), 0 = nothing to do (no images) or STAGED, 1 = TILES.
+// Touches no device.  `factors` / `terms`: the filter's separable factors, for the launch that follows.
+static int h16_plan_2d(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, long long in_pitch, const void *d_out,
+                       int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
+{
+    const char *who = kH16Who2D;
+    if (method == 1) { sg_set_error("%s: method 1 (the dense kernel in the reference's summation order) is not served: the reference has no 16-bit form to be identical to", who); return -1; }
+    if (method < 0 || method > 3) { sg_set_error("%s: method %d is not one of 0, 2, 3", who, method); return -1; }
+    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
+        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who, h16_type_name_2d(in_type),
+                     h16_type_name_2d(out_type), in_type, out_type);
+        return -1;
+    }
+    if (!filter || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (!filter_ok(who, filter)) return -1;
+    const int nx = filter->config.half_window_x, ny = filter->config.half_window_y;
+    if (!geometry_ok(who, nx, ny, rows, cols, in_stride, out_stride, boundary)) return -1;
+    if (images == 0) return 0;
+    const int out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_in), out0 = reinterpret_cast<uintptr_t>(d_out);
+    if (frames_overlap(in0, 2, in_pitch, in_stride, out0, (size_t)out_elem, out_pitch, out_stride, rows, cols, images)) {
+        sg_set_error("%s: input and output frames overlap (2-D filtering cannot run in place; compared byte-wise)", who);
+        return -1;
+    }
+    // the route (sg_2d_h16_host.hpp).  SAVGOL_HIP_2D_H16_TILES is read at every call, not once: tools/time_2d_h16.py times both routes interleaved in
+    // one process (single-threaded; the header says so).  SAVGOL_HIP_ROLL_TILE is read once, where the fp32 launcher reads it (roll_tiles_on, inside
+    // the predicate); the rule names it as a condition of its own, so the shape carries it too.
+    const char *const tiles_text = getenv("SAVGOL_HIP_2D_H16_TILES");
+    static const bool roll_tile_env = [] { const char *e = getenv("SAVGOL_HIP_ROLL_TILE"); return !e || atoi(e) != 0; }();
+    *terms = sep_factors_cached(&filter->config, factors);
+    FrameShapeH16 shape;
+    shape.rows = rows; shape.cols = cols;
+    shape.in_stride = in_stride; shape.in_pitch = in_pitch; shape.out_stride = out_stride; shape.out_pitch = out_pitch;
+    shape.in_base = in0; shape.out_base = out0; shape.out_elem = out_elem;
+    shape.method = method;
+    shape.x_dominant = sg2d_x_dominant(filter->config.deriv_x, filter->config.deriv_y);
+    shape.additive_tile = *terms > 0 && sg2d_launch_rolling_h16(nx > ny ? nx : ny, *terms, nullptr, factors, filter->scale, 0, nullptr) == 0;
+    shape.roll_tile_switch = roll_tile_env;
+    shape.tiles_switch = !tiles_text || atoi(tiles_text) != 0;
+    return frame_plan_h16(shape) == FRAME_H16_TILES ? 1 : 0;
+}
+
+}  // namespace sg
+
+int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
+                                   const void *d_out, int out_type, int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method)
+{
+    float factors[sg::SEP_FACTOR_FLOATS];
+    int terms = 0;
+    return sg::h16_plan_2d(filter, d_in, in_type, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride, (long long)out_image_pitch, images,
+                           (int)boundary, method, factors, &terms);
+}
+
+int savgol2d_apply_batch_h16(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
+                             void *d_out, int out_type, int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method,
+                             void *stream)
+{
+    using namespace sg;
+    const char *who = kH16Who2D;
+    const long long in_pitch = (long long)in_image_pitch, out_pitch = (long long)out_image_pitch;
+    float factors[SEP_FACTOR_FLOATS];
+    int terms = 0;
+    // the refusals, in the order the header gives, and the route: decided before anything touches the device
+    const int route = h16_plan_2d(filter, d_in, in_type, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, factors, &terms);
+    if (route < 0) return -1;
+    if (images == 0) return 0;
+    DeviceCtx *ctx = ctx_get();                               // both routes: the context binds the thread to the library's device, as in the fp32 call
+    if (!ctx) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned short *in = static_cast<const unsigned short *>(d_in);
+    const bool ibf = in_type == SAVGOL_HIP_BF16;
+    const int out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const int nx = filter->config.half_window_x, ny = filter->config.half_window_y, n = nx > ny ? nx : ny;
+    const int bnd = ((int)boundary == SAVGOL2D_BOUNDARY_VALID || (int)boundary == SAVGOL2D_BOUNDARY_REFLECT) ? (int)boundary : SAVGOL2D_BOUNDARY_CONSTANT;
+    if (route == 1) {
+        Job2DH16 job;
+        memset(&job, 0, sizeof(job));
+        job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
+        job.in_pitch = in_pitch; job.out_pitch = out_pitch;
+        job.nx = nx; job.ny = ny; job.boundary = bnd;
+        job.in_bf = ibf ? 1 : 0; job.out_bf = out_type == SAVGOL_HIP_BF16 ? 1 : 0; job.out_f32 = out_type == SAVGOL_HIP_F32 ? 1 : 0;
+        // chunks of images as enqueue_frame cuts them for the twin
+        const size_t max_img = ((size_t)1 << 30) / ((size_t)((cols + 63) / 64) * (size_t)(rows + 1)) + 1;
+        int rc = 0;
+        for (size_t i0 = 0; i0 < images && rc == 0; i0 += max_img) {
+            const unsigned ni = (unsigned)(images - i0 < max_img ? images - i0 : max_img);
+            job.in = in + (long long)i0 * in_pitch;
+            job.out = static_cast<unsigned char *>(d_out) + i0 * (size_t)out_pitch * (size_t)out_elem;
+            rc = sg2d_launch_rolling_h16(n, terms, &job, factors, filter->scale, ni, st);
+            if (rc == 1 && i0 > 0) rc = -1;                  // cannot happen: the first chunk's answer holds for all
+        }
+        if (rc == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
+        if (rc < 0) return -1;
+        // "not covered": nothing has been enqueued -- the staged route
+    }
+    return h16_staged_2d(ctx, filter, in, ibf, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, st);
 }
 
 // ---- device entry points of the derivative frames.  Square windows: a separable frame per output, each through enqueue_frame --

@@ -27,6 +27,10 @@
 #include <utility>
 
 #include "sg_2d.hpp"
+#ifdef SG_ROLL_H16
+#include "sg_2d_h16.hpp"
+#endif
+#include "sg_h16.hpp"
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
 
@@ -140,11 +144,17 @@ __device__ __forceinline__ f32x2 roll_mul_xb(const f32x2 s, const f32x2 x)
 // branch.  2: padded modes, stored quads are whole.  3: VALID, where the stored range starts and ends inside a quad: four range-checked
 // dword stores per row for the lanes that hold such a quad.  (The edge strips on the scalar path cost the tile form 13 %:
 // profiles/r04_2d_tile_experiments.txt.)
-template <int N, int NT, int NOUT, int MODE, bool BOX, bool ACC, int TR = 0>
-__device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT, NOUT> &taps, float *mine, const float *in, float *const (&outs)[NOUT],
+//
+// 16-BIT STORAGE (sg_2d_roll_h16.inc, a build of this file of its own): JOB = Job2DH16, TIN = 16-bit words, TOUT = bytes.  Only load_row and store_row know:
+// a row's quad is one 8-byte load widened exactly, the ring and everything between the two lambdas is the fp32 text below, and the four results are
+// rounded once on their way out.  With JOB = Job2D and float pointers (every fp32 kernel) the text is what it was.
+template <int N, int NT, int NOUT, int MODE, bool BOX, bool ACC, int TR = 0, class JOB, class TIN, class TOUT>
+__device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, NOUT> &taps, float *mine, const TIN *in, TOUT *const (&outs)[NOUT],
                                           int xload, int yb, int nout, int lane, int xlo, int xhi, int ylo, int yhi)
 {
     typedef Roll<N, ACC, TR> R;
+    constexpr bool H16 = !std::is_same<TIN, float>::value;
+    static_assert(!H16 || (MODE != 0 && TR > 0 && NOUT == 1), "16-bit rows: tile form on vector loads only");
     static_assert(!BOX || (NT == 2 && NOUT == 1), "the additive form is one output of two terms");
     static_assert(TR == 0 || !ACC, "tiles are plain passes");
     static_assert(!ACC || (NOUT == 1 && !BOX && !R::STRAIGHT), "accumulating passes are single-output launches of the general form");
@@ -173,8 +183,15 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
     }
     const bool reflect = job.boundary == SAVGOL2D_BOUNDARY_REFLECT;
     auto load_row = [&](int r) -> f32x4 {                    // rows past the band are clamped re-reads that are never used
-        const float *row = in + (long long)fix_row(yb - N + r, job.rows, reflect) * job.in_stride;
-        if constexpr (EDGE) {
+        const TIN *row = in + (long long)fix_row(yb - N + r, job.rows, reflect) * job.in_stride;
+        if constexpr (H16) {                                 // one 8-byte load, widened exactly; the edge strips' remap works on the widened quad
+            const u32x2 raw = *reinterpret_cast<const u32x2 *>(row + (EDGE ? qcol : c0));
+            const f32x2 lo = widen2(raw.x, job.in_bf != 0), hi = widen2(raw.y, job.in_bf != 0);
+            const f32x4 q = f32x4{lo.x, lo.y, hi.x, hi.y};
+            if constexpr (!EDGE) return q;
+            const float nx = fx_w ? q.w : q.x, nw = fx_x ? q.x : q.w;
+            return f32x4{nx, fx_b ? nx : (fx_rev ? q.z : q.y), fx_b ? nx : (fx_rev ? q.y : q.z), nw};
+        } else if constexpr (EDGE) {
             const f32x4 q = *reinterpret_cast<const f32x4 *>(row + qcol);
             const float nx = fx_w ? q.w : q.x, nw = fx_x ? q.x : q.w;          // a broadcast lane has nx == nw == the edge float
             return f32x4{nx, fx_b ? nx : (fx_rev ? q.z : q.y), fx_b ? nx : (fx_rev ? q.y : q.z), nw};
@@ -187,7 +204,11 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
     const __amdgpu_buffer_rsrc_t rsrc_none = __builtin_amdgcn_make_buffer_rsrc(outs[0], 0, 0, 0x00020000);     // zero records: drops every store
     // EDGE: a lane stores its quad when all of it lies in the stored range; PARTIAL: the floats of a quad that straddles the range's end
     const bool whole = !EDGE || (c0 >= xlo && c0 + 4 <= xhi);
-    const unsigned col_off = (out_lane && whole) ? (unsigned)(c0 * 4) : 0x80000000u;
+    // 16-bit rows: bytes per stored element, wave-uniform (2, or 4 for fp32 output); every offset below counts it where the fp32 text has its 4
+    int es = 4;
+    if constexpr (H16) es = job.out_f32 ? 4 : 2;
+    unsigned col_off = (out_lane && whole) ? (unsigned)(c0 * 4) : 0x80000000u;
+    if constexpr (H16) col_off = (out_lane && whole) ? (unsigned)(c0 * es) : 0x80000000u;
     // (their four dword stores go through a per-row descriptor that spans exactly the row's stored range [xlo, xhi): the hardware range
     //  check drops the floats outside it.  One offset register per float, each laundered: left to see that the four offsets are
     //  consecutive, hipcc merges the four dword stores into ONE dwordx4 store, whose range check then passes or fails as a whole --
@@ -196,14 +217,17 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
     if constexpr (PARTIAL) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (out_lane && !whole) pcol_off[j] = (unsigned)((c0 - xlo + j) * 4);
+            if constexpr (H16) { if (out_lane && !whole) pcol_off[j] = (unsigned)((c0 - xlo + j) * es); }
+            else if (out_lane && !whole) pcol_off[j] = (unsigned)((c0 - xlo + j) * 4);
             asm volatile("" : "+v"(pcol_off[j]));
         }
     }
     if constexpr (VEC && R::STRAIGHT) {
 #pragma unroll
-        for (int o = 0; o < NOUT; ++o)
-            rsrc[o] = __builtin_amdgcn_make_buffer_rsrc(outs[o], 0, (int)((long long)job.rows * job.out_stride * 4), 0x00020000);
+        for (int o = 0; o < NOUT; ++o) {
+            if constexpr (H16) rsrc[o] = __builtin_amdgcn_make_buffer_rsrc(outs[o], 0, (int)((long long)job.rows * job.out_stride * es), 0x00020000);
+            else rsrc[o] = __builtin_amdgcn_make_buffer_rsrc(outs[o], 0, (int)((long long)job.rows * job.out_stride * 4), 0x00020000);
+        }
     }
     float *const wr = mine + 4 * R::HL + 4 * lane;           // where this lane's vertical results go
     const float *const rd = mine + 4 * lane;                 // where its horizontal window starts
@@ -392,7 +416,7 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
     static_assert(!ACC || (R::U % PR == 0 && R::P >= LEAD), "slot = row % PR must carry over from one group of U rows to the next");
     f32x4 prevq[PR];
     auto load_prev = [&](int yo) -> f32x4 {
-        const float *orow = outs[0] + (long long)(yo < job.rows ? yo : job.rows - 1) * job.out_stride;
+        const TOUT *orow = outs[0] + (long long)(yo < job.rows ? yo : job.rows - 1) * job.out_stride;
         if constexpr (VEC) return *reinterpret_cast<const f32x4 *>(orow + c0);
         else {
             const bool row_ok = yo >= ylo && yo < yhi;
@@ -412,6 +436,29 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
             // or without the row part added) is fixed for the item; the row part is wave-uniform: one v_add per row.  A row
             // nobody stores selects the empty descriptor (scalar select).
             const bool keep_row = yo >= ylo && yo < yhi && yo < yend;                     // uniform
+            if constexpr (H16) {
+                // The storage type of the output is wave-uniform, and a branch on it would be a branch in the tile: BOTH stores are issued, the one of
+                // the other type through the empty descriptor.  16 -> 16 bit: the four results rounded once to nearest even, two dwords, ONE 8-byte
+                // store (lane offset c0 * 2, row part yo * out_stride * 2); 16 bit -> fp32: the fp32 tile's store.
+                const f32x4 v4 = f32x4{r[0].x, r[0].y, r[1].x, r[1].y};
+                const u32x2 pk = u32x2{narrow2(r[0], job.out_bf != 0), narrow2(r[1], job.out_bf != 0)};
+                const int off = (int)(col_off + (unsigned)(yo * job.out_stride * es));
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v4), (keep_row && job.out_f32) ? rsrc[o] : rsrc_none, off, 0, 2 /* nt */);
+                __builtin_amdgcn_raw_buffer_store_b64(pk, (keep_row && !job.out_f32) ? rsrc[o] : rsrc_none, off, 0, 2 /* nt */);
+                if constexpr (PARTIAL) {
+                    // VALID's partial quads: four 2-byte (fp32 output: 4-byte) range-checked stores through the row's descriptor over [xlo, xhi) elements
+                    const float v[4] = {r[0].x, r[0].y, r[1].x, r[1].y};
+                    const unsigned short h[4] = {(unsigned short)(pk.x & 0xffffu), (unsigned short)(pk.x >> 16), (unsigned short)(pk.y & 0xffffu), (unsigned short)(pk.y >> 16)};
+                    const __amdgpu_buffer_rsrc_t prow = __builtin_amdgcn_make_buffer_rsrc(outs[o] + ((long long)yo * job.out_stride + xlo) * es, 0,
+                                                                                          keep_row ? (xhi - xlo) * es : 0, 0x00020000);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[j]), job.out_f32 ? prow : rsrc_none, (int)pcol_off[j], 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b16(h[j], job.out_f32 ? rsrc_none : prow, (int)pcol_off[j], 0, 0);
+                    }
+                }
+                return;
+            }
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{r[0].x, r[0].y, r[1].x, r[1].y}), keep_row ? rsrc[o] : rsrc_none,
                                                    (int)(col_off + (unsigned)(yo * job.out_stride * 4)), 0, 2 /* nt */);
             if constexpr (PARTIAL) {
@@ -423,7 +470,7 @@ __device__ __forceinline__ void roll_item(const Job2D &job, const RollTaps<N, NT
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[j]), prow, (int)pcol_off[j], 0, 0);
             }
         } else if (yo >= ylo && yo < yhi && yo < yend) {     // uniform
-            float *orow = outs[o] + (long long)yo * job.out_stride;
+            TOUT *orow = outs[o] + (long long)yo * job.out_stride;
             if constexpr (VEC) {
                 if (out_lane)
                     __builtin_nontemporal_store(__builtin_bit_cast(u32x4, f32x4{r[0].x, r[0].y, r[1].x, r[1].y}),
@@ -861,6 +908,11 @@ static int dispatch_roll2(int n, int terms, const Job2D &job, const float *f0, f
     else return 1;
 }
 
+#ifdef SG_ROLL_H16
+// The 16-bit-storage build of this file (Makefile, ROLL_H16_RULE): the additive tile on 16-bit rows and its launcher under the name SEP_ROLL_FN, in
+// place of the fp32 entry points.  Everything above is shared text; no fp32 kernel is instantiated in this build.
+#include "sg_2d_roll_h16.inc"
+#else
 // 0 = launched, 1 = this object does not cover the case (half window outside SEP_ROLL_MIN_N..SEP_ROLL_MAX_N, no
 // definite parity).  Built once per half-window group (Makefile), each under its own name SEP_ROLL_FN.
 int SEP_ROLL_FN(int n, int terms, const Job2D &job, const float *factors, float scale, unsigned images, int cu_count, hipStream_t st)
@@ -876,6 +928,8 @@ int SEP_ROLL_FN2(int n, int terms, const Job2D &job, const float *factors0, floa
     if (n < SEP_ROLL_MIN_N || n > SEP_ROLL_MAX_N || terms < 1 || terms > roll_max_terms(n, 2)) return 1;
     return dispatch_roll2<SEP_ROLL_MIN_N, 1>(n, terms, job, factors0, scale0, factors1, scale1, out1, images, cu_count, st);
 }
+
+#endif  // SG_ROLL_H16
 
 #ifdef SG_STAMPS2D
 }  // namespace sg
