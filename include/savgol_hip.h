@@ -12,7 +12,7 @@
  * 0 on success and -1 on error unless stated otherwise; savgol_hip_last_error() has the text.
  * Launches are asynchronous on `stream`.  What "enqueue only" means, entry point by entry point:
  *   - savgol_apply[_valid]_batch_f32/f64, savgol_apply[_valid]_multi_batch_f32, savgol2d_apply_batch_f32, savgol2d_gradient/hessian/laplacian_batch_f32 (square and
- *     rectangular windows), savgol_streambank_push/_push_full/_push_block/_flush/_flush_leading/_reset: launches only --
+ *     rectangular windows), savgol_streambank_push/_push_full/_push_block/_push_block_multi/_flush/_flush_leading/_reset: launches only --
  *     capturable into a hipGraph AFTER one warm-up call with the same filter: the FIRST call with a new filter content
  *     uploads its tables (hipMalloc + a synchronous hipMemcpy, then cached for the life of the process; tables are never
  *     freed or moved, so captured graphs and queued launches stay valid) and, for the derivative frames, solves the
@@ -360,6 +360,31 @@ int    savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_sampl
  * device; the tick service running.  ticks == 0 returns 0. */
 int    savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_samples, int in_type, size_t ticks,
                                         void *d_out, int out_type, void *stream);
+/* The FUSED MULTI-OUTPUT block push: `count` banks (1..4) take the same block of samples, which is read from memory once -- value, velocity and
+ * acceleration of the same sensor streams move 4 + 4 * count bytes per stream-tick instead of 8 * count.
+ * `banks` and `d_outs` are host arrays of `count` entries; the banks are ordinary banks (savgol_streambank_create / _create_ex), each with its own
+ * filter, ring and counters, all with the same `streams`.  d_samples is one block [ticks][streams]; d_outs[k] is bank k's output block, same pitch.
+ * The banks need not share a history, a filter order, a derivative or a time_step.
+ * CONTRACT.  Let bank k's twin be a bank of the same configuration, flags and history that takes savgol_streambank_push_block(twin, d_samples, ticks,
+ * d_outs[k], stream).  Output k equals the twin's output bit for bit (NaN positions coincide, NaN payloads are free); rows of ticks without an output
+ * are not written; bank k's counters, write position and ring are the twin's (the savgol_streambank_save blobs are byte-equal); produced[k] is the
+ * twin's return value (`produced` may be NULL).  No tolerance anywhere.  Returns the smallest produced[k], -1 on error; ticks == 0 returns 0.
+ * Two routes, chosen before anything is enqueued (csrc/sg_stream_host.hpp, block_plan_multi).  FUSED needs all of: count >= 2; every bank the same
+ * half window n and the same SAVGOL_STREAMBANK_FMA flag; n <= 8 (both bank kinds, two and three outputs per launch); streams % 128 == 0; the
+ * samples and every output 16-byte aligned; more than 64 ticks; every bank's own block push takes its tap-by-tap LDS-DMA tiles.  Then every bank's
+ * first 64 ticks go through its own tiles on its own ring, the rest of the block through one launch that reads each row once and feeds every output
+ * (two or three outputs: one launch; four: two launches of two; csrc/sg_stream_dma_multi.hip), and every ring takes its newest samples.  Every other
+ * call is `count` single block pushes in the caller's order.  The call only enqueues and allocates nothing: capturable after one warm-up call.
+ * Returns -1 with a text naming the call, before any launch, every bank untouched; checked in this order: NULL banks / d_outs / d_samples; count
+ * outside 1..4; a NULL banks[k] or d_outs[k]; a bank listed twice; a bank with another `streams` than banks[0]; a bank on another device or with
+ * the tick service running; more than 2^30 ticks; d_outs[k] sharing a byte with the samples or with an earlier d_outs[j].
+ * _route enqueues nothing and changes nothing: -1 on the refusals above, else the number of fused launches the call would make (0: the call is
+ * `count` single block pushes). */
+#define SAVGOL_STREAM_MULTI_MAX_BANKS 4
+int    savgol_streambank_push_block_multi(SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks,
+                                          float *const *d_outs, int *produced, void *stream);
+int    savgol_streambank_push_block_multi_route(SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks,
+                                                float *const *d_outs);
 /* trailing / leading edge rows, up to n of them; -1 on bad arguments, 0 if never filled       */
 int    savgol_streambank_flush(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream);
 int    savgol_streambank_flush_leading(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream);

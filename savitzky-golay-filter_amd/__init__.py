@@ -144,6 +144,8 @@ SIGNATURES = {
     "savgol_streambank_push_full": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "savgol_streambank_push_block": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "savgol_streambank_push_block_h16": (C.c_int, [_vp, _vp, C.c_int, _sz, _vp, C.c_int, _vp]),
+    "savgol_streambank_push_block_multi": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, C.POINTER(C.c_int), _vp]),
+    "savgol_streambank_push_block_multi_route": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp]),
     "savgol_streambank_flush": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_flush_leading": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_ready": (C.c_bool, [_vp]),
@@ -512,6 +514,28 @@ class StreamBank:
     def load(self, blob, stream=None):
         if lib().savgol_streambank_load(self.ptr, blob.ctypes.data, _stream(stream)) != 0:
             raise RuntimeError(last_error())
+
+
+def _multi_args(banks, outs):
+    if len(banks) != len(outs):
+        raise ValueError(f"push_block_multi: {len(banks)} banks, {len(outs)} outputs")
+    return (C.c_void_p * len(banks))(*[getattr(b, "ptr", b) for b in banks]), (C.c_void_p * len(outs))(*[_addr(o) for o in outs])
+
+
+def push_block_multi(banks, samples, ticks, outs, stream=None):
+    """savgol_streambank_push_block_multi: up to four StreamBanks take the same block of samples, read from memory once; outs[k] is bank k's output
+    block.  Returns the list of produced counts, one per bank (each the single savgol_streambank_push_block's return value); raises on a refusal."""
+    b, o = _multi_args(banks, outs)
+    produced = (C.c_int * max(len(banks), 1))()
+    if lib().savgol_streambank_push_block_multi(b, len(banks), _addr(samples), ticks, o, produced, _stream(stream)) < 0:
+        raise RuntimeError(last_error())
+    return list(produced)[:len(banks)]
+
+
+def push_block_multi_route(banks, samples, ticks, outs):
+    """the number of fused launches push_block_multi would make on these arguments (0 = one single block push per bank), -1 on a refusal; enqueues nothing"""
+    b, o = _multi_args(banks, outs)
+    return lib().savgol_streambank_push_block_multi_route(b, len(banks), _addr(samples), ticks, o)
 
 
 class Filter2D:

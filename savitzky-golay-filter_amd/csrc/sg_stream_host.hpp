@@ -1,6 +1,7 @@
 // sg_stream_host.hpp -- host-only rules of the stream block push (no device types: included by g++ translation units too): which form a call takes
 // (block_form), the geometry of its tiles or bands, how taps are packed, the wait counts of the LDS-DMA tiles (DmaQueue) and the routes of the 16-bit
-// call (block_plan_h16).  tests/mock/stream_block_forms.cpp, stream_block_h16.cpp and dma_queue.cpp print them for tables of call shapes.
+// call (block_plan_h16) and of the fused multi-output call (block_plan_multi).  tests/mock/stream_block_forms.cpp, stream_block_h16.cpp,
+// stream_block_multi.cpp, dma_queue.cpp and dma_queue_multi.cpp print them for tables of call shapes.
 #pragma once
 
 #include <cstddef>
@@ -117,10 +118,11 @@ inline BlockForm block_form(int n, bool fma, size_t streams, size_t ticks, unsig
 // ---- LDS-DMA tiles (sg_stream_dma.hpp): compile-time bookkeeping, plain constexpr so that tests/mock/dma_queue.cpp can hold it to a simulated queue ----
 // vmcnt bookkeeping.  A DMA instruction moves RPD rows (2 rows of 512 bytes: fp32 rows; 4 rows of 256 bytes: 16-bit rows); a step consumes the RPD rows of
 // one DMA.  The wave's vector-memory queue, in issue order: the DP DMAs of the prologue, then per step j: the stores of the outputs that rows RPD j ..
-// RPD j + RPD - 1 finish, then DMA j + DP (if it exists).  ROWS = TR + 2N is rounded up to whole DMAs (pad rows finish no output).
-template <int N, int TR, int DP, int RPD = 2> struct DmaQueue {
+// RPD j + RPD - 1 finish, then DMA j + DP (if it exists).  ROWS = TR + 2N is rounded up to whole DMAs (pad rows finish no output).  A finished output
+// row issues SPR stores: 1, or one per output of the fused multi-output tiles (sg_stream_dma_multi.hip).
+template <int N, int TR, int DP, int RPD = 2, int SPR = 1> struct DmaQueue {
     static constexpr int NI = (TR + 2 * N + RPD - 1) / RPD;
-    static constexpr int done(int r) { return r - 2 * N < 0 ? 0 : (r - 2 * N > TR ? TR : r - 2 * N); }     // outputs finished by rows < r = stores issued
+    static constexpr int done(int r) { return SPR * (r - 2 * N < 0 ? 0 : (r - 2 * N > TR ? TR : r - 2 * N)); }     // stores issued by the outputs that rows < r finish
     static constexpr int dmas(int a, int b) { int c = 0; for (int j = a; j < b; ++j) c += (j >= 0 && j + DP < NI) ? 1 : 0; return c; }  // DMAs issued by steps [a, b)
     // operations younger than DMA p when step g starts (p = g + 1 is the one step g waits for)
     static constexpr int younger(int p, int g)
@@ -205,6 +207,64 @@ inline H16Plan block_plan_h16(int n, bool fma, size_t streams, size_t ticks, uns
     plan.chunk = 0;
     plan.wpb = shape.wpb;
     if (plan.body) plan.grid = tile_geom(streams, 128, plan.body, 32, shape.group, shape.wpb, &plan.geo);
+    return plan;
+}
+
+// ---- the fused multi-output block push (savgol_streambank_push_block_multi): count banks, one read of the block.  Decided before anything is enqueued ----
+// FUSED needs all of: count >= 2; every bank the same half window n and the same SAVGOL_STREAMBANK_FMA flag; n <= stream_multi_max_n(bank kind, outputs
+// per launch); tiles_take(streams, 128, misaligned, ticks, 64) with `misaligned` or-ed over the samples, every output and every ring; ticks > 64; block_form
+// answers DMA_TILES for every bank (tap by tap, not the block moments; both switches as sg_bank_roll_launch reads them); the twin's and the body's tile
+// counts are indexed by 32 bits.  2 or 3 outputs are one launch, 4 are two launches of two (as savgol_apply_multi_batch_f32).  A fused call is, per bank,
+// a head of 64 ticks through the bank's own fp32 tiles (sg_bank_roll_launch: the twin's bands 0 and 1, the only ones that read the ring since 2n <= 64),
+// then the body's tiles of all outputs in `launches` launches (bands >= 2 of the twin's tile order), then per bank the tail store.
+// SINGLE (launches == 0): everything else -- `count` single block pushes in the caller's order.
+// Shipped bounds: 8 for both bank kinds and for 2 and 3 outputs per launch -- at every fused shape the call's median is 1.18-1.66 x ahead of the single
+// calls on config 3's shape (profiles/stream_multi_time.txt); nothing above 8 has been measured.
+constexpr int STREAM_MULTI_MAX_BANKS = 4;
+constexpr int stream_multi_max_n(bool fma, int outputs) { return (outputs == 2 || outputs == 3) ? (fma ? 8 : 8) : 0; }   // (fused bank : bit-exact bank)
+// (waves per block, ring pairs) of a multi-output launch: launch_bank_dma_shape's values for the half windows the call fuses -- the ring is per wave and
+// shared by the outputs, the accumulators stay within 256 VGPRs (two waves per SIMD, what these block shapes hold anyway).  The swapped table
+// -- (8, 12) for the light tiles, (4, 16) for the fused bank above n = 5 -- measured level, 0.97-1.02, interleaved in one process (EXPERIMENTS)
+struct MultiTileShape { int wpb, dp; };
+constexpr MultiTileShape multi_tile_shape(int n, bool fma, int /* outputs */) { return n > 5 && fma ? MultiTileShape{8, 12} : MultiTileShape{4, 16}; }
+struct MultiBank { int n; bool fma, centre; };
+struct MultiPlan {
+    int      launches;               // 0 = `count` single calls
+    int      per[2];                 // outputs of each launch, banks in the caller's order
+    size_t   head, body;             // fused: 64 and ticks - 64
+    TileGeom geo;                    // the body's tiles ...
+    unsigned grid;                   // ... and their grid
+    int      wpb, dp;
+};
+// moment_terms(k): the host fit of bank k's taps, asked only where block_form asks
+template <class Fit>
+inline MultiPlan block_plan_multi(const MultiBank *banks, int count, size_t streams, size_t ticks, unsigned misaligned, bool dma_switch, bool moment_switch,
+                                  Fit &&moment_terms)
+{
+    MultiPlan plan = {};
+    if (count < 2 || count > STREAM_MULTI_MAX_BANKS) return plan;
+    const int per0 = count == 4 ? 2 : count;
+    const int n = banks[0].n;
+    const bool fma = banks[0].fma;
+    for (int k = 1; k < count; ++k)
+        if (banks[k].n != n || banks[k].fma != fma) return plan;
+    if (n < 1 || n > stream_multi_max_n(fma, per0)) return plan;
+    if (!tiles_take(streams, 128, misaligned, ticks, STREAM_DMA_MIN_TICKS) || ticks <= STREAM_DMA_MIN_TICKS) return plan;
+    for (int k = 0; k < count; ++k)
+        if (block_form(n, fma, streams, ticks, misaligned, banks[k].centre, dma_switch, moment_switch, [&] { return moment_terms(k); }) != DMA_TILES) return plan;
+    const DmaTileShape twin = dma_tile_shape(DMA_TILES, n, fma, streams);
+    TileGeom whole;
+    if (!tile_geom(streams, 128, ticks, 32, twin.group, twin.wpb, &whole)) return plan;      // the twin itself would leave the tiles
+    const MultiTileShape shape = multi_tile_shape(n, fma, per0);
+    plan.head = STREAM_DMA_MIN_TICKS;
+    plan.body = ticks - STREAM_DMA_MIN_TICKS;
+    plan.wpb = shape.wpb;
+    plan.dp = shape.dp;
+    plan.grid = tile_geom(streams, 128, plan.body, 32, twin.group, shape.wpb, &plan.geo);
+    if (!plan.grid) return plan;
+    plan.launches = count == 4 ? 2 : 1;
+    plan.per[0] = per0;
+    plan.per[1] = count == 4 ? 2 : 0;
     return plan;
 }
 
