@@ -23,6 +23,8 @@
  *     synchronise); savgol2d_apply_rowband_f32 and channels longer than 2^30 samples use the same pool for their scratch;
  *   - savgol_streambank_push_block_h16: launches plus ONE stream-ordered allocation / free pair from the same pool (the fp32 frames of its head, or
  *     of the staged route's chunk); capturable after one warm-up call like savgol_streambank_push_block;
+ *   - savgol_streambank_push_block_multi_h16: a fused call makes launches plus ONE such pair (the two fp32 frames of its head, shared by the banks);
+ *     a call that falls back is `count` savgol_streambank_push_block_h16 calls; capturable after one warm-up call;
  *   - savgol_streambank_save/_load, savgol_hip_synchronize and every host-pointer drop-in call of savgolFilter.h /
  *     savgol_stream.h / savgol2d.h: synchronous by nature (they return host data).
  * Short host-pointer calls (savgol_apply / _valid / _strided on <= 4096 samples and <= 64 K multiply-adds, every savgol_stream_* call
@@ -385,6 +387,37 @@ int    savgol_streambank_push_block_multi(SavgolStreamBank *const *banks, int co
                                           float *const *d_outs, int *produced, void *stream);
 int    savgol_streambank_push_block_multi_route(SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks,
                                                 float *const *d_outs);
+/* The FUSED MULTI-OUTPUT block push on 16-bit STORAGE: both of the above at once -- `count` banks (1..4) take the same block of fp16 or bf16 samples,
+ * which is read from memory once, and write outputs of the same type or fp32: value, velocity and acceleration of the same sensor streams move
+ * 2 + 2 * count bytes per stream-tick (16 -> 16 bit) instead of 4 * count, or 2 + 4 * count (16 bit -> fp32) instead of 6 * count.
+ * `banks` and `d_outs` are host arrays of `count` entries; the banks are ordinary banks (fp32 rings), all with the same `streams`.  ONE in_type and ONE
+ * out_type serve every output, as in savgol_apply_multi_batch_h16; the served pairs are savgol_streambank_push_block_h16's (f16 -> f16, bf16 -> bf16,
+ * f16 -> f32, bf16 -> f32).  d_samples is one block [ticks][streams] of in_type; d_outs[k] is bank k's output block of out_type, same pitch in elements.
+ * The banks need not share a history, a filter order, a derivative or a time_step.
+ * CONTRACT.  Let bank k's twin be a bank of the same configuration, flags and history that takes the single savgol_streambank_push_block_h16(twin,
+ * d_samples, in_type, ticks, d_outs[k], out_type, stream).  Output k equals the twin's output bit for bit, byte for byte (NaN positions coincide, NaN
+ * payloads are free); rows of ticks without an output are not written; bank k's counters, write position and ring are the twin's (the
+ * savgol_streambank_save blobs are byte-equal); produced[k] is the twin's return value (`produced` may be NULL).  By the single call's own contract
+ * every output is therefore also savgol_streambank_push_block_multi's output on the samples widened exactly to fp32, rounded ONCE to nearest even.
+ * No tolerance anywhere.  Returns the smallest produced[k], -1 on error; ticks == 0 returns 0.
+ * Two routes, chosen before anything is enqueued (csrc/sg_stream_host.hpp, block_plan_multi_h16).  FUSED needs all of: count >= 2; every bank the same
+ * half window n and the same SAVGOL_STREAMBANK_FMA flag; n <= 8 (both bank kinds, two and three outputs per launch); streams % 128 == 0; the samples,
+ * every output and every ring 16-byte aligned; more than 64 ticks; every bank's twin takes its tap-by-tap LDS-DMA tiles.  Then the first 64 ticks are
+ * widened once into fp32 scratch and go, bank after bank, through the bank's own fp32 tiles on its own ring and are rounded out (the twin's own head);
+ * the rest of the block goes through one launch that reads each 16-bit row once and feeds every output (two or three outputs: one launch; four: two
+ * launches of two; csrc/sg_stream_dma_multi_h16.hip); every ring takes its newest samples.  Every other call is `count` single
+ * savgol_streambank_push_block_h16 calls in the caller's order.  A fused call makes launches plus ONE stream-ordered allocation / free pair from the
+ * library's pool, like the single 16-bit call: capturable after one warm-up call.
+ * Returns -1 with a text naming the call, before any launch or scratch allocation, every bank untouched; checked in this order: NULL banks / d_outs /
+ * d_samples; count outside 1..4; a NULL banks[k] or d_outs[k]; an unserved type pair (named; f32 -> anything included); a bank listed twice; a bank
+ * with another `streams` than banks[0]; a bank on another device or with the tick service running; more than 2^30 ticks; d_outs[k] sharing a byte with
+ * the samples or with an earlier d_outs[j] (compared byte-wise, each buffer with its own element size).
+ * _route enqueues nothing and changes nothing: -1 on the refusals above, else the number of fused launches the call would make (0: the call is
+ * `count` single 16-bit block pushes). */
+int    savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
+                                              void *const *d_outs, int out_type, int *produced, void *stream);
+int    savgol_streambank_push_block_multi_h16_route(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
+                                                    void *const *d_outs, int out_type);
 /* trailing / leading edge rows, up to n of them; -1 on bad arguments, 0 if never filled       */
 int    savgol_streambank_flush(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream);
 int    savgol_streambank_flush_leading(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream);

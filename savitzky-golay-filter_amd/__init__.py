@@ -146,6 +146,8 @@ SIGNATURES = {
     "savgol_streambank_push_block_h16": (C.c_int, [_vp, _vp, C.c_int, _sz, _vp, C.c_int, _vp]),
     "savgol_streambank_push_block_multi": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, C.POINTER(C.c_int), _vp]),
     "savgol_streambank_push_block_multi_route": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp]),
+    "savgol_streambank_push_block_multi_h16": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _sz, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
+    "savgol_streambank_push_block_multi_h16_route": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _sz, _vp, C.c_int]),
     "savgol_streambank_flush": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_flush_leading": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_ready": (C.c_bool, [_vp]),
@@ -536,6 +538,33 @@ def push_block_multi_route(banks, samples, ticks, outs):
     """the number of fused launches push_block_multi would make on these arguments (0 = one single block push per bank), -1 on a refusal; enqueues nothing"""
     b, o = _multi_args(banks, outs)
     return lib().savgol_streambank_push_block_multi_route(b, len(banks), _addr(samples), ticks, o)
+
+
+def _multi_h16_types(dtype, out_dtype):
+    out_dtype = dtype if out_dtype is None else out_dtype
+    if dtype not in _STORAGE or out_dtype not in _STORAGE:
+        raise ValueError(f"push_block_multi_h16: dtype {dtype!r} -> {out_dtype!r}")
+    return _STORAGE[dtype], _STORAGE[out_dtype]
+
+
+def push_block_multi_h16(banks, samples, dtype, ticks, outs, out_dtype=None, stream=None):
+    """savgol_streambank_push_block_multi_h16: up to four StreamBanks take the same block of fp16 / bf16 samples (dtype "f16" / "bf16"), read from memory
+    once; outs[k] is bank k's output block of out_dtype (None = the same type, or "f32").  Returns the list of produced counts, one per bank (each the
+    single savgol_streambank_push_block_h16's return value); raises on a refusal."""
+    b, o = _multi_args(banks, outs)
+    it, ot = _multi_h16_types(dtype, out_dtype)
+    produced = (C.c_int * max(len(banks), 1))()
+    if lib().savgol_streambank_push_block_multi_h16(b, len(banks), _addr(samples), it, ticks, o, ot, produced, _stream(stream)) < 0:
+        raise RuntimeError(last_error())
+    return list(produced)[:len(banks)]
+
+
+def push_block_multi_h16_route(banks, samples, dtype, ticks, outs, out_dtype=None):
+    """the number of fused launches push_block_multi_h16 would make on these arguments (0 = one single 16-bit block push per bank), -1 on a refusal;
+    enqueues nothing"""
+    b, o = _multi_args(banks, outs)
+    it, ot = _multi_h16_types(dtype, out_dtype)
+    return lib().savgol_streambank_push_block_multi_h16_route(b, len(banks), _addr(samples), it, ticks, o, ot)
 
 
 class Filter2D:

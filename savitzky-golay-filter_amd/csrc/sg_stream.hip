@@ -34,6 +34,7 @@
 #include "sg_stream.hpp"
 #include "sg_stream_h16.hpp"
 #include "sg_stream_multi.hpp"
+#include "sg_stream_multi_h16.hpp"
 #include "sg_stream_roll.hpp"
 
 extern "C" int sg_small_stream_rows(void *ctx, const float *d_table, const float *ring, int ws, int wp, float dt_inv, int count, const int *row,
@@ -1047,6 +1048,181 @@ int savgol_streambank_push_block_multi(SavgolStreamBank *const *banks, int count
             int all = first[k];
             if (k >= k0) {
                 const int rc = savgol_streambank_push_block(banks[k], d_samples + plan.head * streams, plan.body, d_outs[k] + plan.head * streams, stream);
+                if (rc < 0) return -1;
+                all += rc;
+            }
+            first[k] = all;
+        }
+    }
+    for (int k = 0; k < count; ++k) {
+        if (produced) produced[k] = first[k];
+        least = first[k] < least ? first[k] : least;
+    }
+    return least;
+}
+
+// ---- savgol_streambank_push_block_multi_h16 ----
+namespace {
+// every refusal of the call and of its route query, in the header's order, then the plan; false = refused (text set), nothing enqueued or changed
+bool multi_h16_prepare(const char *who, SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks, void *const *d_outs,
+                       int out_type, MultiCall *call)
+{
+    if (!banks || !d_outs || !d_samples) { sg_set_error("%s: NULL pointer", who); return false; }
+    if (count < 1 || count > SAVGOL_STREAM_MULTI_MAX_BANKS) {
+        sg_set_error("%s: count %d is outside 1..%d", who, count, SAVGOL_STREAM_MULTI_MAX_BANKS);
+        return false;
+    }
+    for (int k = 0; k < count; ++k) {
+        if (!banks[k]) { sg_set_error("%s: NULL pointer: banks[%d]", who, k); return false; }
+        if (!d_outs[k]) { sg_set_error("%s: NULL pointer: d_outs[%d]", who, k); return false; }
+    }
+    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
+        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who,
+                     h16_type_name(in_type), h16_type_name(out_type), in_type, out_type);
+        return false;
+    }
+    for (int k = 1; k < count; ++k)
+        for (int j = 0; j < k; ++j)
+            if (banks[k] == banks[j]) { sg_set_error("%s: banks[%d] and banks[%d] are the same bank (a bank is listed twice)", who, j, k); return false; }
+    for (int k = 1; k < count; ++k)
+        if (banks[k]->streams != banks[0]->streams) {
+            sg_set_error("%s: banks[%d] has %zu streams, banks[0] has %zu (the banks of one call share the samples)", who, k, banks[k]->streams, banks[0]->streams);
+            return false;
+        }
+    for (int k = 0; k < count; ++k)
+        if (!sg::bank_on_current_device(banks[k], who)) return false;
+    if (ticks > ((size_t)1 << 30)) { sg_set_error("%s: %zu ticks in one call, more than 2^30: split the call", who, ticks); return false; }
+    const size_t streams = banks[0]->streams;
+    // not in place and no two outputs on one byte; compared byte-wise, the element sizes may differ
+    const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * (out_type == SAVGOL_HIP_F32 ? 4 : 2);
+    const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples);
+    for (int k = 0; k < count && in_bytes; ++k) {
+        const uintptr_t out0 = reinterpret_cast<uintptr_t>(d_outs[k]);
+        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
+            sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of an output may not share a byte)",
+                         who, k, in_bytes, out_bytes);
+            return false;
+        }
+        for (int j = 0; j < k; ++j) {
+            const uintptr_t o = reinterpret_cast<uintptr_t>(d_outs[j]);
+            if (o < out0 + out_bytes && out0 < o + out_bytes) {
+                sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes %llu bytes of its own)", who, j, k, out_bytes);
+                return false;
+            }
+        }
+    }
+    // the route, decided before anything is enqueued (sg_stream_host.hpp).  Centring and the two switches as sg_bank_roll_launch reads them.
+    static const int dma_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }();
+    static const int moment_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
+    uintptr_t low = in0;
+    for (int k = 0; k < count; ++k) {
+        const SavgolFilter *f = banks[k]->filter;
+        const int n = f->config.half_window;
+        const bool fma = (banks[k]->flags & SAVGOL_STREAMBANK_FMA) != 0;
+        double wsum = 0.0, wabs = 0.0;
+        for (int i = 0; i <= 2 * n; ++i) { wsum += (double)f->center_weights[i]; wabs += std::fabs((double)f->center_weights[i]); }
+        call->bank[k] = sg::MultiBank{n, fma, fma && std::fabs(wsum) < 1e-3 * wabs};
+        call->wsum[k] = (float)wsum;
+        low |= reinterpret_cast<uintptr_t>(d_outs[k]) | reinterpret_cast<uintptr_t>(banks[k]->d_ring);
+    }
+    sg::StreamMomentFit fit;
+    call->plan = sg::block_plan_multi_h16(call->bank, count, streams, ticks, (unsigned)(low & 15u), dma_env != 0, moment_env != 0,
+                                          [&](int k) { return sg::stream_moment_fit(call->bank[k].n, banks[k]->filter->center_weights, &fit); });
+    return true;
+}
+}  // namespace
+
+int savgol_streambank_push_block_multi_h16_route(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
+                                                 void *const *d_outs, int out_type)
+{
+    MultiCall call;
+    if (!multi_h16_prepare("savgol_streambank_push_block_multi_h16_route", banks, count, d_samples, in_type, ticks, d_outs, out_type, &call)) return -1;
+    return ticks == 0 ? 0 : call.plan.launches;
+}
+
+int savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
+                                           void *const *d_outs, int out_type, int *produced, void *stream)
+{
+    const char *who = "savgol_streambank_push_block_multi_h16";
+    MultiCall call;
+    if (!multi_h16_prepare(who, banks, count, d_samples, in_type, ticks, d_outs, out_type, &call)) return -1;
+    if (produced) for (int k = 0; k < count; ++k) produced[k] = 0;
+    if (ticks == 0) return 0;
+    int least = 0x7fffffff;
+    const sg::MultiPlan &plan = call.plan;
+    if (plan.launches == 0) {                                // `count` single 16-bit calls, in the caller's order
+        for (int k = 0; k < count; ++k) {
+            const int rc = savgol_streambank_push_block_h16(banks[k], d_samples, in_type, ticks, d_outs[k], out_type, stream);
+            if (rc < 0) return -1;
+            if (produced) produced[k] = rc;
+            least = rc < least ? rc : least;
+        }
+        return least;
+    }
+
+    sg::DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned short *samples = static_cast<const unsigned short *>(d_samples);
+    const size_t streams = banks[0]->streams, out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const int n = call.bank[0].n;
+    const bool fma = call.bank[0].fma, ibf = in_type == SAVGOL_HIP_BF16;
+    // ---- head: rows 0..63 widened once for all banks; then every bank's own fp32 tiles of bands 0 and 1 on its own ring, rounded out (the twin's own
+    // head: its silent ticks, ring reads and centring).  One allocation / free pair from the pool, the output frame reused bank after bank ----
+    const size_t head = plan.head, frame = head * streams * sizeof(float);                  // streams % 128 == 0: the second frame stays aligned
+    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, who));
+    if (!scratch) return -1;
+    float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
+    h16_widen(samples, sin, head * streams, ibf, st);
+    for (int k = 0; k < count; ++k) {
+        SavgolStreamBank *b = banks[k];
+        if (sg::sg_bank_roll_launch(n, b->filter->center_weights, b->d_ring, sin, sout, streams, b->wp, b->received, head, b->dt_inv, fma ? 1 : 0, ctx->cu_count, st) != 0) {
+            // nothing of bank k or the banks behind it is enqueued and no counter has moved: the heads already enqueued wrote only rows the call owns
+            (void)sg::scratch_free(scratch, st, who);
+            sg_set_error("%s: no kernel for half_window %d", who, n);
+            return -1;
+        }
+        const unsigned long long ws = (unsigned long long)b->filter->window_size;
+        const size_t silent = b->received + 1 >= ws ? 0 : (size_t)(ws - 1 - b->received);         // head ticks without an output (<= 2n <= 64)
+        h16_round(sout, d_outs[k], streams, silent, head, out_type, st);
+    }
+    const bool freed = sg::scratch_free(scratch, st, who);
+    // ---- body: bands >= 2 of all outputs, one launch of 2 or 3, or two launches of two ----
+    int covered = 0, k0 = 0;
+    for (int l = 0; l < plan.launches && covered == 0; ++l) {
+        const int per = plan.per[l];
+        sg::BankJobMultiH16 job;
+        memset(&job, 0, sizeof(job));
+        const float *center[sg::STREAM_MULTI_PER_LAUNCH] = {};
+        job.samples = samples; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
+        job.in_type = (unsigned)in_type; job.out_type = (unsigned)out_type;
+        for (int j = 0; j < per; ++j) {
+            const SavgolStreamBank *b = banks[k0 + j];
+            job.out[j] = d_outs[k0 + j]; job.dt_inv[j] = b->dt_inv; job.centre_sum[j] = call.wsum[k0 + j]; job.centre[j] = call.bank[k0 + j].centre ? 1 : 0;
+            center[j] = b->filter->center_weights;
+        }
+        covered = (fma ? sg::sg_bank_dma_multi_h16_launch_fma : sg::sg_bank_dma_multi_h16_launch_ref)(n, per, center, job, plan, st);
+        if (covered == 0) k0 += per;
+    }
+    const dim3 tail_grid((unsigned)((streams + 255) / 256), 8);
+    // ---- tail: the newest samples, widened, into every ring, the counters once per bank ----
+    int first[SAVGOL_STREAM_MULTI_MAX_BANKS] = {};
+    bool rest = false;
+    for (int k = 0; k < count; ++k) {
+        SavgolStreamBank *b = banks[k];
+        // banks whose body launch the runtime refused: the head becomes a finished 64-tick push, the rest of the call goes through single 16-bit calls
+        const size_t done = k < k0 ? ticks : head;
+        hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, tail_grid, dim3(256), 0, st, b->d_ring, samples, streams, b->filter->window_size, b->wp, done, ibf ? 1 : 0);
+        first[k] = bank_advance(b, done);
+        rest = rest || done < ticks;
+    }
+    if (!freed || !sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block_multi_h16 launch")) return -1;
+    if (rest) {
+        for (int k = 0; k < count; ++k) {
+            int all = first[k];
+            if (k >= k0) {
+                const int rc = savgol_streambank_push_block_h16(banks[k], samples + head * streams, in_type, plan.body,
+                                                                static_cast<char *>(d_outs[k]) + head * streams * out_elem, out_type, stream);
                 if (rc < 0) return -1;
                 all += rc;
             }

@@ -1,7 +1,8 @@
 // sg_stream_host.hpp -- host-only rules of the stream block push (no device types: included by g++ translation units too): which form a call takes
 // (block_form), the geometry of its tiles or bands, how taps are packed, the wait counts of the LDS-DMA tiles (DmaQueue) and the routes of the 16-bit
-// call (block_plan_h16) and of the fused multi-output call (block_plan_multi).  tests/mock/stream_block_forms.cpp, stream_block_h16.cpp,
-// stream_block_multi.cpp, dma_queue.cpp and dma_queue_multi.cpp print them for tables of call shapes.
+// call (block_plan_h16), of the fused multi-output call (block_plan_multi) and of the fused multi-output call on 16-bit storage (block_plan_multi_h16).
+// tests/mock/stream_block_forms.cpp, stream_block_h16.cpp, stream_block_multi.cpp, stream_block_multi_h16.cpp, dma_queue.cpp, dma_queue_multi.cpp and
+// dma_queue_multi_h16.cpp print them for tables of call shapes.
 #pragma once
 
 #include <cstddef>
@@ -260,6 +261,61 @@ inline MultiPlan block_plan_multi(const MultiBank *banks, int count, size_t stre
     plan.body = ticks - STREAM_DMA_MIN_TICKS;
     plan.wpb = shape.wpb;
     plan.dp = shape.dp;
+    plan.grid = tile_geom(streams, 128, plan.body, 32, twin.group, shape.wpb, &plan.geo);
+    if (!plan.grid) return plan;
+    plan.launches = count == 4 ? 2 : 1;
+    plan.per[0] = per0;
+    plan.per[1] = count == 4 ? 2 : 0;
+    return plan;
+}
+
+// ---- the fused multi-output block push on 16-bit storage (savgol_streambank_push_block_multi_h16).  Decided before anything is enqueued ----
+// The conjunction of what block_plan_multi and block_plan_h16 demand.  FUSED needs all of: count >= 2; every bank the same half window n and the same
+// SAVGOL_STREAMBANK_FMA flag; n <= stream_multi_h16_max_n(bank kind, outputs per launch); tiles_take(streams, 128, misaligned, ticks, 64) with
+// `misaligned` or-ed over the 16-bit sample base, every output base and every ring; ticks > 64; block_form answers DMA_TILES for every bank's twin (the
+// fp32 call on aligned buffers: tap by tap, not the block moments); the twin's and the body's tile counts are indexed by 32 bits.  2 or 3 outputs are one
+// launch, 4 are two launches of two.  A fused call is a head of 64 ticks -- widened once into fp32 scratch, then per bank its own fp32 tiles on its own
+// ring (the twin's bands 0 and 1) and the rounding of their rows --, the body's tiles of all outputs in `launches` launches (sg_stream_dma_multi_h16.hip:
+// bands >= 2 of the twins' tile order), then per bank the tail store.
+// SINGLE (launches == 0): everything else -- `count` single savgol_streambank_push_block_h16 calls in the caller's order.
+// A table of its own, not stream_multi_max_n: the measurement may lower it per (bank kind, outputs per launch).  Shipped bounds: 8 for both bank
+// kinds and for 2 and 3 outputs per launch -- at every fused shape the call's median is 1.12-1.52 x ahead of the single 16-bit calls on config 3's shape
+// (profiles/stream_multi_h16_time.txt, part 1); nothing above 8 has been measured.
+constexpr int stream_multi_h16_max_n(bool fma, int outputs) { return (outputs == 2 || outputs == 3) ? (fma ? 8 : 8) : 0; }   // (fused bank : bit-exact bank)
+// (waves per block, ring ROWS) of a launch.  The starting table was multi_tile_shape's waves with the fp32 multi tile's ring depth in rows -- half the
+// KiB, a DMA moves four 256-byte rows (as the single 16-bit tiles took launch_bank_dma_shape's): (4, 32), and (8, 24) for the fused bank
+// above n = 5.  Interleaved with a second build in one process (profiles/stream_multi_h16_time.txt, second part), (4, 32) is ahead of (8, 24) outside
+// the +- 3 % spread on 16 -> 16 bit for the fused bank with three outputs from n = 6 (1.05-1.21 x) and with two outputs from n = 7 (1.05-1.13 x) and
+// level to 6 % behind on 16 bit -> fp32; at (fused bank, n = 6, two outputs) and on every light tile the starting table is level or ahead and stays.
+struct MultiH16TileShape { int wpb, rows; };
+constexpr MultiH16TileShape multi_h16_tile_shape(int n, bool fma, int outputs)
+{
+    return fma && n == 6 && outputs == 2 ? MultiH16TileShape{8, 24} : MultiH16TileShape{4, 32};
+}
+// the plan is block_plan_multi's struct; dp counts DMAs of four rows
+template <class Fit>
+inline MultiPlan block_plan_multi_h16(const MultiBank *banks, int count, size_t streams, size_t ticks, unsigned misaligned, bool dma_switch, bool moment_switch,
+                                      Fit &&moment_terms)
+{
+    MultiPlan plan = {};
+    if (count < 2 || count > STREAM_MULTI_MAX_BANKS) return plan;
+    const int per0 = count == 4 ? 2 : count;
+    const int n = banks[0].n;
+    const bool fma = banks[0].fma;
+    for (int k = 1; k < count; ++k)
+        if (banks[k].n != n || banks[k].fma != fma) return plan;
+    if (n < 1 || n > stream_multi_h16_max_n(fma, per0)) return plan;
+    if (!tiles_take(streams, 128, misaligned, ticks, STREAM_DMA_MIN_TICKS) || ticks <= STREAM_DMA_MIN_TICKS) return plan;
+    for (int k = 0; k < count; ++k)
+        if (block_form(n, fma, streams, ticks, 0u, banks[k].centre, dma_switch, moment_switch, [&] { return moment_terms(k); }) != DMA_TILES) return plan;
+    const DmaTileShape twin = dma_tile_shape(DMA_TILES, n, fma, streams);
+    TileGeom whole;
+    if (!tile_geom(streams, 128, ticks, 32, twin.group, twin.wpb, &whole)) return plan;      // the twin itself would leave the tiles
+    const MultiH16TileShape shape = multi_h16_tile_shape(n, fma, per0);
+    plan.head = STREAM_DMA_MIN_TICKS;
+    plan.body = ticks - STREAM_DMA_MIN_TICKS;
+    plan.wpb = shape.wpb;
+    plan.dp = shape.rows / 4;
     plan.grid = tile_geom(streams, 128, plan.body, 32, twin.group, shape.wpb, &plan.geo);
     if (!plan.grid) return plan;
     plan.launches = count == 4 ? 2 : 1;
