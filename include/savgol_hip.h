@@ -21,6 +21,8 @@
  *     otherwise (reference summation order, unaligned or overlapping fields) launches plus a stream-ordered allocation /
  *     free pair for its two dense frames, from the library's own retained memory pool (no shared scratch, no lock, no
  *     synchronise); savgol2d_apply_rowband_f32 and channels longer than 2^30 samples use the same pool for their scratch;
+ *   - savgol_apply_strided_multi_batch_f32: a fused call (savgol_apply_strided_multi_batch_f32_route > 0) makes launches only and allocates nothing --
+ *     capturable after one warm-up call with the same filters; a call that falls back is `njobs` savgol_apply_strided_batch_f32_ex calls;
  *   - savgol_streambank_push_block_h16: launches plus ONE stream-ordered allocation / free pair from the same pool (the fp32 frames of its head, or
  *     of the staged route's chunk); capturable after one warm-up call like savgol_streambank_push_block;
  *   - savgol_streambank_push_block_multi_h16: a fused call makes launches plus ONE such pair (the two fp32 frames of its head, shared by the banks);
@@ -208,6 +210,35 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter,
                                       const void *d_in, size_t in_stride, size_t in_offset, size_t in_channel_pitch,
                                       void *d_out, size_t out_stride, size_t out_offset, size_t out_channel_pitch,
                                       size_t channels, size_t count, unsigned flags, void *stream);
+/* Several FIELDS of the records from one pass: job k applies jobs[k].filter to the field at in_offset of every record of the input grid
+ * (d_in, in_stride, in_channel_pitch) and writes the field at out_offset of the output grid (d_out, out_stride, out_channel_pitch); offsets are bytes
+ * inside a record.  Jobs may share an input field (value, velocity and acceleration of one field); d_out may be d_in (the in-place array-of-structs
+ * case).  `flags` is a complete SAVGOL_BATCH_* word, those of savgol_apply_strided_batch_f32_ex.
+ * CONTRACT: the call leaves memory as `njobs` calls of savgol_apply_strided_batch_f32_ex(jobs[k].filter, d_in, in_stride, jobs[k].in_offset, ..., flags)
+ * in the caller's order would leave it, BIT FOR BIT: NaN positions coincide, and bytes no job writes (other fields, the slack between `count` records
+ * and the channel pitch, anything outside the grids) stay as they were.
+ * Refusals, -1 with a text naming this call, before any device call and with nothing written, in this order: 1. unknown flags, or TILE_NARROW with
+ * TILE_WIDE;  2. NULL jobs, d_in or d_out;  3. njobs outside 1..SAVGOL_STRIDED_MULTI_MAX_JOBS;  4. a NULL jobs[k].filter (k ascending);  5. a
+ * filter struct that is not a valid SavgolFilter (k ascending);  6. count below a job's window size (k ascending).  channels == 0 returns 0.
+ * FUSED (one pass over the records per launch, sg1d_strided_multi_kernel) needs all of: njobs >= 2; every filter the same half_window; under
+ * SAVGOL_BATCH_BOUNDARY_AWARE the same config.boundary; no SAVGOL_BATCH_REFERENCE_SUMMATION; every field address, both strides and both channel pitches
+ * multiples of 4 and both strides >= 4; count <= 2^30; no output field sharing a byte with any job's input field or another job's output field (one
+ * record grid with offsets at least 4 bytes apart cyclically, or two grids that do not overlap at all); record sizes inside the measured table (equal
+ * strides of 8, 12, 16, 20, 32 or 64 bytes: DESIGN.md 4.1f).  A fused call runs the jobs in order in launches of at most 4 jobs, a last group of one
+ * job as a single call.  Every other call IS the `njobs` single calls in order -- which is also what gives a job that reads an earlier job's output
+ * its sequential meaning.
+ * _route: what the call would do, enqueuing nothing and needing no device: the number of fused launches, 0 = njobs single calls (or channels == 0),
+ * -1 = refused with the same text.                                                                                                              */
+enum { SAVGOL_STRIDED_MULTI_MAX_JOBS = 16 };
+typedef struct { const SavgolFilter *filter; size_t in_offset, out_offset; } SavgolFieldJob;   /* byte offsets inside a record */
+int savgol_apply_strided_multi_batch_f32(const SavgolFieldJob *jobs, int njobs,
+                                         const void *d_in, size_t in_stride, size_t in_channel_pitch,
+                                         void *d_out, size_t out_stride, size_t out_channel_pitch,
+                                         size_t channels, size_t count, unsigned flags, void *stream);
+int savgol_apply_strided_multi_batch_f32_route(const SavgolFieldJob *jobs, int njobs,
+                                               const void *d_in, size_t in_stride, size_t in_channel_pitch,
+                                               void *d_out, size_t out_stride, size_t out_channel_pitch,
+                                               size_t channels, size_t count, unsigned flags);
 /* Several filters on ONE batch in one pass: smoothing and derivatives (d = 0 / 1 / 2 ...) of the same signals read the input once.
  * `filters` and `d_outs` are host arrays of `count` entries, 1 <= count <= SAVGOL_MULTI_MAX_FILTERS; d_outs[k] is a device pointer and every
  * output has the pitch out_ld.  All filters share config.half_window and config.boundary (poly_order, derivative and time_step may differ;

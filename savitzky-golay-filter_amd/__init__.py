@@ -33,6 +33,7 @@ SAVGOL_STREAMBANK_FMA = 1
 SAVGOL_BATCH_REFERENCE_SUMMATION, SAVGOL_BATCH_PLAIN_SUMMATION, SAVGOL_BATCH_TILE_NARROW, SAVGOL_BATCH_TILE_WIDE = 1, 2, 4, 8
 SAVGOL_BATCH_CORRECT_LEADING_EDGE, SAVGOL_BATCH_BOUNDARY_AWARE, SAVGOL_BATCH_MOMENT_F64 = 16, 32, 64
 SAVGOL_MULTI_MAX_FILTERS = 4
+SAVGOL_STRIDED_MULTI_MAX_JOBS = 16
 SAVGOL_HIP_F32, SAVGOL_HIP_F16, SAVGOL_HIP_BF16 = 0, 1, 2          # storage type of a device buffer (savgol_apply[_valid]_batch_h16)
 _STORAGE = {"f32": SAVGOL_HIP_F32, "f16": SAVGOL_HIP_F16, "bf16": SAVGOL_HIP_BF16}
 
@@ -46,6 +47,10 @@ class SavgolFilter(C.Structure):
     _fields_ = [("config", SavgolConfig), ("window_size", C.c_int), ("dt_scale", C.c_float),
                 ("center_weights", C.c_float * SAVGOL_MAX_WINDOW),
                 ("edge_weights", (C.c_float * SAVGOL_MAX_WINDOW) * SAVGOL_MAX_HALF_WINDOW)]
+
+
+class SavgolFieldJob(C.Structure):
+    _fields_ = [("filter", C.POINTER(SavgolFilter)), ("in_offset", C.c_size_t), ("out_offset", C.c_size_t)]
 
 
 class SavgolStream(C.Structure):
@@ -127,6 +132,8 @@ SIGNATURES = {
     "savgol_apply_valid_batch_f32_ex": (C.c_int, [_F, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_batch_f64_ex": (C.c_int, [_F, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_strided_batch_f32_ex": (C.c_int, [_F, _vp, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_strided_multi_batch_f32": (C.c_int, [C.POINTER(SavgolFieldJob), C.c_int, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_strided_multi_batch_f32_route": (C.c_int, [C.POINTER(SavgolFieldJob), C.c_int, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, C.c_uint]),
     "savgol_apply_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
@@ -369,6 +376,26 @@ def apply_multi_batch(filters, d_in, d_outs, channels, length, in_ld=None, out_l
         rc = getattr(lib(), name)(fs, count, _addr(d_in), outs, channels, length, in_ld, out_ld, flags, _stream(stream))
     if rc != 0:
         raise RuntimeError(f"{name} returned {rc}: {last_error()}")
+
+
+def _field_jobs(jobs):
+    return (SavgolFieldJob * max(len(jobs), 1))(*[SavgolFieldJob(f.ptr, in_offset, out_offset) for f, in_offset, out_offset in jobs])
+
+
+def apply_strided_multi_batch(jobs, d_in, in_stride, in_channel_pitch, d_out, out_stride, out_channel_pitch, channels, count, flags=0, stream=None):
+    """savgol_apply_strided_multi_batch_f32: several fields of an array of structs from one pass.  jobs: [(Filter, in_offset, out_offset)], byte offsets
+    inside a record; job k filters the field at in_offset of the grid (d_in, in_stride, in_channel_pitch) into the field at out_offset of the grid
+    (d_out, out_stride, out_channel_pitch).  Memory is left as the single strided calls in this order would leave it, bit for bit."""
+    rc = lib().savgol_apply_strided_multi_batch_f32(_field_jobs(jobs), len(jobs), _addr(d_in), in_stride, in_channel_pitch, _addr(d_out), out_stride,
+                                                    out_channel_pitch, channels, count, flags, _stream(stream))
+    if rc != 0:
+        raise RuntimeError(f"savgol_apply_strided_multi_batch_f32 returned {rc}: {last_error()}")
+
+
+def apply_strided_multi_batch_route(jobs, d_in, in_stride, in_channel_pitch, d_out, out_stride, out_channel_pitch, channels, count, flags=0):
+    """what the call above would do, without a device: the number of fused launches, 0 = len(jobs) single calls, -1 = refused (last_error() has the text)"""
+    return lib().savgol_apply_strided_multi_batch_f32_route(_field_jobs(jobs), len(jobs), _addr(d_in), in_stride, in_channel_pitch, _addr(d_out), out_stride,
+                                                            out_channel_pitch, channels, count, flags)
 
 
 def apply_multi_tensor(filters, x, valid=False, flags=0, stream=None, out_dtype=None):

@@ -17,6 +17,7 @@
 #include "sg_k1d_host.hpp"
 #include "sg_k1d_h16_host.hpp"
 #include "sg_k1d_multi_h16_host.hpp"
+#include "sg_k1d_strided_multi_launch.hpp"
 #include "sg_runtime.hpp"
 
 using sg::DeviceCtx;
@@ -1261,6 +1262,118 @@ int savgol_apply_strided_batch_f32_ex(const SavgolFilter *filter, const void *d_
     }
     if (!sg::scratch_free(dense, st, "scratch free (strided staging)")) rc = -1;
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Several record fields from one pass (savgol_apply_strided_multi_batch_f32).  The call leaves memory as `njobs` calls of
+// savgol_apply_strided_batch_f32_ex in the caller's order would; ONE rule (sg::strided_multi_plan, sg_k1d_strided_multi_host.hpp) says whether it IS
+// those calls or runs sg1d_strided_multi_kernel, and the call and its _route twin both ask it.
+// ------------------------------------------------------------------------------------------------
+static_assert(SAVGOL_STRIDED_MULTI_MAX_JOBS == sg::STRIDED_MULTI_MAX_JOBS, "the header's bound is the rule's");
+
+// The refusals, in the header's order, then the rule.  -1 = refused (text set), 0 = nothing to do (channels == 0), 1 = *plan says how.
+static int strided_multi_front(const char *who, const SavgolFieldJob *jobs, int njobs, const void *d_in, size_t in_stride, size_t in_channel_pitch,
+                               const void *d_out, size_t out_stride, size_t out_channel_pitch, size_t channels, size_t count, unsigned flags,
+                               sg::StridedMultiPlan *plan)
+{
+    if (!flags_ok(who, flags)) return -1;
+    if (!jobs || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (njobs < 1 || njobs > SAVGOL_STRIDED_MULTI_MAX_JOBS) { sg_set_error("%s: njobs %d outside 1..%d", who, njobs, (int)SAVGOL_STRIDED_MULTI_MAX_JOBS); return -1; }
+    for (int k = 0; k < njobs; ++k)
+        if (!jobs[k].filter) { sg_set_error("%s: NULL pointer (jobs[%d].filter)", who, k); return -1; }
+    for (int k = 0; k < njobs; ++k)
+        if (!filter_sane(jobs[k].filter, who)) return -1;
+    for (int k = 0; k < njobs; ++k)
+        if (count < (size_t)jobs[k].filter->window_size) { sg_set_error("%s: count < window size (jobs[%d])", who, k); return -1; }
+    if (channels == 0) return 0;
+    sg::StridedMultiField fields[SAVGOL_STRIDED_MULTI_MAX_JOBS];
+    for (int k = 0; k < njobs; ++k)
+        fields[k] = sg::StridedMultiField{(int)jobs[k].filter->config.half_window, (int)jobs[k].filter->config.boundary,
+                                          (uintptr_t)d_in + jobs[k].in_offset, (uintptr_t)d_out + jobs[k].out_offset};
+    *plan = sg::strided_multi_plan(fields, njobs, in_stride, in_channel_pitch, out_stride, out_channel_pitch, channels, count,
+                                   (flags & SAVGOL_BATCH_BOUNDARY_AWARE) != 0, (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) != 0);
+    return 1;
+}
+
+// one fused launch (per channel group): jobs[0 .. nj) of one half window, every field the single call's job word for word
+static int strided_multi_group(DeviceCtx *ctx, const SavgolFieldJob *jobs, int nj, const void *d_in, size_t in_stride, size_t in_channel_pitch, void *d_out,
+                               size_t out_stride, size_t out_channel_pitch, size_t channels, size_t count, unsigned flags, hipStream_t st)
+{
+    const int n = jobs[0].filter->config.half_window;
+    const Variant variant = (flags & SAVGOL_BATCH_BOUNDARY_AWARE) ? FULL : FULL_POLY_EDGES;
+    const CallShape shape = call_shape(jobs[0].filter, variant, count);         // the jobs share the half window and, where it counts, the boundary mode
+    sg::JobStridedMulti job;
+    sg::TapsStridedMulti taps;
+    memset(&job, 0, sizeof(job));
+    memset(&taps, 0, sizeof(taps));
+    job.njobs = (unsigned)nj;
+    job.grid.in_pitch = (long long)in_channel_pitch; job.grid.out_pitch = (long long)out_channel_pitch;
+    job.grid.in_stride = (long long)in_stride; job.grid.out_stride = (long long)out_stride;
+    job.grid.length = (unsigned)count;
+    const unsigned TW = 64u * (unsigned)sg::VPL_NARROW * 4u;
+    job.grid.tiles_per_channel = (unsigned)((count + TW - 1) / TW);
+    sg::division_magic(job.grid.tiles_per_channel, &job.grid.tpc_magic, &job.grid.tpc_shift);
+    job.grid.store_lo = shape.store_lo;
+    job.grid.store_hi = shape.store_hi;
+    job.grid.flags = shape.mode_flags;
+    for (int k = 0; k < nj; ++k) {
+        const SavgolFilter *f = jobs[k].filter;
+        const CallShape sk = call_shape(f, variant, count);
+        const FilterPlan *plan = plan_get(ctx, f, sk.want_edges ? NEED_EDGES : 0u);
+        if (!plan) return -1;
+        const OutputPart o = output_part(f, sk, flags, false, false);
+        job.in_off[k] = (long long)jobs[k].in_offset;
+        job.out_off[k] = (long long)jobs[k].out_offset;
+        job.dt_inv[k] = o.dt_inv;
+        job.flags[k] = sk.mode_flags | o.flags;
+        job.edges[k] = sk.want_edges ? plan->d_edges : nullptr;
+        taps.t[k] = plan->taps32;
+    }
+    for (ChannelGroups g{channels, launch_max_channels(job.grid.tiles_per_channel, 2u * (unsigned)nj)}; g.next();) {
+        job.grid.in = static_cast<const char *>(d_in) + g.c0 * in_channel_pitch;
+        job.grid.out = static_cast<char *>(d_out) + g.c0 * out_channel_pitch;
+        job.grid.total_tiles = (unsigned)(g.nc * job.grid.tiles_per_channel);
+        job.grid.edge_items = shape.want_edges ? (unsigned)(2 * g.nc * (size_t)nj) : 0u;      // end e of job k rides at e * njobs + k
+        if (sg1d_launch_strided_multi(n, &job, &taps, sg::strided_multi_grid_blocks(job.grid.total_tiles + job.grid.edge_items), st) != 0) return -1;
+    }
+    return 0;
+}
+
+int savgol_apply_strided_multi_batch_f32_route(const SavgolFieldJob *jobs, int njobs, const void *d_in, size_t in_stride, size_t in_channel_pitch,
+                                               void *d_out, size_t out_stride, size_t out_channel_pitch, size_t channels, size_t count, unsigned flags)
+{
+    sg::StridedMultiPlan plan = {};
+    const int go = strided_multi_front("savgol_apply_strided_multi_batch_f32", jobs, njobs, d_in, in_stride, in_channel_pitch, d_out, out_stride,
+                                       out_channel_pitch, channels, count, flags, &plan);
+    return go <= 0 ? go : plan.launches;
+}
+
+int savgol_apply_strided_multi_batch_f32(const SavgolFieldJob *jobs, int njobs, const void *d_in, size_t in_stride, size_t in_channel_pitch, void *d_out,
+                                         size_t out_stride, size_t out_channel_pitch, size_t channels, size_t count, unsigned flags, void *stream)
+{
+    const char *who = "savgol_apply_strided_multi_batch_f32";
+    sg::StridedMultiPlan plan = {};
+    const int go = strided_multi_front(who, jobs, njobs, d_in, in_stride, in_channel_pitch, d_out, out_stride, out_channel_pitch, channels, count, flags, &plan);
+    if (go <= 0) return go;
+    auto single = [&](int k) {
+        return savgol_apply_strided_batch_f32_ex(jobs[k].filter, d_in, in_stride, jobs[k].in_offset, in_channel_pitch, d_out, out_stride, jobs[k].out_offset,
+                                                 out_channel_pitch, channels, count, flags, stream);
+    };
+    if (plan.launches == 0) {                       // the single calls in the caller's order: the contract itself
+        for (int k = 0; k < njobs; ++k)
+            if (single(k) != 0) return -1;
+        return 0;
+    }
+    if (!sg1d_launch_strided_multi) { sg_set_error("%s: the multi-field strided kernels are not in this build (object not linked)", who); return -1; }
+    DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    for (int g = 0, k0 = 0; g < plan.groups; k0 += plan.per[g], ++g) {
+        const int rc = plan.per[g] == 1 ? single(k0)
+                                        : strided_multi_group(ctx, jobs + k0, plan.per[g], d_in, in_stride, in_channel_pitch, d_out, out_stride, out_channel_pitch,
+                                                              channels, count, flags, static_cast<hipStream_t>(stream));
+        if (rc != 0) return -1;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
