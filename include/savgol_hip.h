@@ -285,13 +285,41 @@ int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int c
  * Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for 16-bit rows, 16 for fp32 output) move as vectors; any
  * other base or pitch is served element by element.  Like the single calls it only enqueues (after one warm-up call with the same filter), so it
  * can be captured into a graph.  Several filters on one read of 16-bit rows: savgol_apply[_valid]_multi_batch_h16 below.  Not served in 16 bit: the strided path,
- * the 2-D derivative-frame and row-band calls, int16 samples, fp32 -> 16-bit pairs.  The stream bank's block push on 16-bit rows:
+ * the 2-D derivative-frame and row-band calls, fp32 -> 16-bit pairs (int16 samples: savgol_apply[_valid]_batch_i16 below).  The stream bank's block push on 16-bit rows:
  * savgol_streambank_push_block_h16 below; the 2-D batch call on 16-bit frames: savgol2d_apply_batch_h16 below. */
 enum { SAVGOL_HIP_F32 = 0, SAVGOL_HIP_F16 = 1, SAVGOL_HIP_BF16 = 2 };   /* storage type of a device buffer */
 int savgol_apply_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
                            size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
 /* the same with savgol_apply_valid's outputs: length - 2n elements at d_out[c*out_ld + 0..] */
 int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type,
+                                 size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
+
+/* int16 STORAGE for the 1-D batch call: int16 samples (ADC / DAQ / audio counts) in device memory, fp32 arithmetic inside.  4 bytes per sample
+ * (int16 -> int16) or 6 (int16 -> fp32) instead of a widening pass plus the fp32 call's 8.
+ * d_in points to rows of int16 elements, d_out to rows of `out_type` elements: SAVGOL_HIP_I16 or SAVGOL_HIP_F32.  in_ld and out_ld count elements
+ * of their own buffer.  Every input element is widened exactly to fp32 while its tile is staged and the tile runs the fp32 path unchanged
+ * (three-chain sum; block moments from half window 20 where the fp32 call takes them; centred tiles for derivative filters; dt scaling;
+ * POLYNOMIAL edge rows in the same launch) on the narrow tile.
+ * CONTRACT: the output equals, bit for bit, savgol_apply[_valid]_batch_f32_ex(filter, widen(d_in), ..., flags | SAVGOL_BATCH_TILE_NARROW), where
+ * widen is the exact int16 -> fp32 conversion.  For out_type F32 it is that call's output itself (NaN positions coincide; NaN payloads are free).
+ * For out_type I16 each fp32 result is converted ONCE, just before it is stored: rounded to nearest, ties to even; saturated to
+ * [-32768, 32767], so +-Inf saturate; NaN gives 0.
+ * `flags` is a complete SAVGOL_BATCH_* word, as in the _ex calls: SAVGOL_BATCH_PLAIN_SUMMATION, SAVGOL_BATCH_TILE_NARROW (implied) and
+ * SAVGOL_BATCH_CORRECT_LEADING_EDGE are served.
+ * Returns -1 with a text naming the call, before any device call; the checks run in this order and the first fault wins:
+ *   1. flags: SAVGOL_BATCH_REFERENCE_SUMMATION, then SAVGOL_BATCH_TILE_WIDE, then flags of other calls (BOUNDARY_AWARE, MOMENT_F64), then unknown bits;
+ *   2. an out_type other than SAVGOL_HIP_I16 / SAVGOL_HIP_F32;
+ *   3. a NULL pointer, then length < window, then channels longer than 2^30 samples, then a pitch smaller than the row;
+ *   4. input and output rows that share a byte (compared byte-wise: the element sizes may differ; in place is not served).
+ * channels == 0 returns 0.  Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for int16 rows, 16 for fp32
+ * output) move as vectors; any other base or pitch is served element by element.  Like its siblings it only enqueues (after one warm-up call with
+ * the same filter), so it can be captured into a graph.  Not served on int16: uint16 samples, a gain or offset per call or channel,
+ * int16 -> fp16 / bf16 outputs, the multi-output, strided, stream-bank and 2-D calls, in place. */
+enum { SAVGOL_HIP_I16 = 3 };   /* joins SAVGOL_HIP_F32 / _F16 / _BF16 */
+int savgol_apply_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type,
+                           size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
+/* the same with savgol_apply_valid's outputs: length - 2n elements at d_out[c*out_ld + 0..] */
+int savgol_apply_valid_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type,
                                  size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
 
 /* Several filters on ONE batch of 16-bit rows in one pass: the multi-output call on 16-bit storage.  2 + 2 count bytes per input sample

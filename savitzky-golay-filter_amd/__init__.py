@@ -36,6 +36,7 @@ SAVGOL_MULTI_MAX_FILTERS = 4
 SAVGOL_STRIDED_MULTI_MAX_JOBS = 16
 SAVGOL_HIP_F32, SAVGOL_HIP_F16, SAVGOL_HIP_BF16 = 0, 1, 2          # storage type of a device buffer (savgol_apply[_valid]_batch_h16)
 _STORAGE = {"f32": SAVGOL_HIP_F32, "f16": SAVGOL_HIP_F16, "bf16": SAVGOL_HIP_BF16}
+SAVGOL_HIP_I16 = 3                                                  # int16 samples (savgol_apply[_valid]_batch_i16); not a type of the 16-bit float calls
 
 
 class SavgolConfig(C.Structure):
@@ -137,6 +138,8 @@ SIGNATURES = {
     "savgol_apply_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_multi_batch_f32": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_batch_i16": (C.c_int, [_F, _vp, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_valid_batch_i16": (C.c_int, [_F, _vp, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_multi_batch_h16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.c_int, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_multi_batch_h16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.c_int, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
@@ -349,6 +352,33 @@ class Filter:
         y = torch.empty((ch, out_len), dtype=x.dtype if out_dtype is None else out_dtype, device=x.device)
         self.apply_batch(x, y, ch, length, length, out_len, dtype=dtype, valid=valid, stream=stream, flags=flags,
                          out_dtype=None if out_dtype is None else names[out_dtype])
+        return y
+
+    def apply_batch_i16(self, d_in, d_out, channels, length, in_ld=None, out_ld=None, out_dtype="i16", valid=False, stream=None, flags=0):
+        """savgol_apply[_valid]_batch_i16: int16 rows in, out_dtype "i16" or "f32" out, fp32 arithmetic; the fp32 narrow-tile call's bits on the widened
+        input, for "i16" rounded to nearest even and saturated (NaN gives 0).  flags is the call's complete SAVGOL_BATCH_* word; in_ld / out_ld count
+        elements of their own buffer."""
+        types = {"i16": SAVGOL_HIP_I16, "f32": SAVGOL_HIP_F32}
+        if out_dtype not in types:
+            raise ValueError(f"apply_batch_i16: out_dtype {out_dtype!r} (\"i16\" or \"f32\")")
+        name = f"savgol_apply_{'valid_' if valid else ''}batch_i16"
+        rc = getattr(lib(), name)(self.ptr, _addr(d_in), _addr(d_out), types[out_dtype], channels, length, length if in_ld is None else in_ld,
+                                  (length - 2 * self.n if valid else length) if out_ld is None else out_ld, flags, _stream(stream))
+        if rc != 0:
+            raise RuntimeError(f"{name} returned {rc}: {last_error()}")
+
+    def apply_tensor_i16(self, x, valid=False, flags=0, out_dtype=None, stream=None):
+        """x: contiguous 2-D torch.int16 tensor [channels, length] on the GPU.  out_dtype: None = int16, or torch.float32."""
+        import torch
+        if x.dtype != torch.int16:
+            raise TypeError(f"apply_tensor_i16 serves int16 tensors, not {x.dtype}")
+        if out_dtype not in (None, torch.int16, torch.float32):
+            raise TypeError(f"apply_tensor_i16: {x.dtype} -> {out_dtype} is not served")
+        assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
+        ch, length = x.shape
+        out_len = length - 2 * self.n if valid else length
+        y = torch.empty((ch, out_len), dtype=torch.int16 if out_dtype is None else out_dtype, device=x.device)
+        self.apply_batch_i16(x, y, ch, length, length, out_len, out_dtype="f32" if out_dtype == torch.float32 else "i16", valid=valid, stream=stream, flags=flags)
         return y
 
 

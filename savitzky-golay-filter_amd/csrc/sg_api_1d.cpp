@@ -16,6 +16,7 @@
 
 #include "sg_k1d_host.hpp"
 #include "sg_k1d_h16_host.hpp"
+#include "sg_k1d_i16_host.hpp"
 #include "sg_k1d_multi_h16_host.hpp"
 #include "sg_k1d_strided_multi_launch.hpp"
 #include "sg_runtime.hpp"
@@ -798,6 +799,75 @@ int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in
 }
 
 // ------------------------------------------------------------------------------------------------
+// int16 storage (savgol_apply[_valid]_batch_i16): int16 rows in, int16 or fp32 out, on the kernels of sg_k1d_i16.hpp.  enqueue_h16's job, field for
+// field -- the one enqueue_batch<float> builds for the widened input under SAVGOL_BATCH_TILE_NARROW -- with element sizes 2 -> 2 or 4, plus the output
+// type.  The checks, in this order (the first fault wins), all before the first device call:
+//   1. flags: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the output type;
+//   3. check_rows: NULL pointer, length < window, channels beyond 2^30 samples, pitches;   (zero channels: 0, nothing enqueued)
+//   4. input and output rows that share a byte;   5. the kernel objects are linked;   6. a usable device.
+// ------------------------------------------------------------------------------------------------
+const char *i16_storage_name(int t)
+{
+    return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_I16 ? "i16" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown";
+}
+
+constexpr const char *I16_TOO_LONG = "%s: channels longer than 2^30 samples (%zu) are not served on int16 storage";
+
+int enqueue_i16(const char *who, const SavgolFilter *f, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
+                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+{
+    if (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) {
+        sg_set_error("%s: SAVGOL_BATCH_REFERENCE_SUMMATION is not served on int16 storage (the reference has no int16 form to be identical to)", who);
+        return -1;
+    }
+    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on int16 storage (the call runs the narrow tile)", who); return -1; }
+    if (flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64)) {
+        sg_set_error("%s: flags 0x%x belong to other calls (BOUNDARY_AWARE: strided calls, MOMENT_F64: fp64 calls)", who, flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64));
+        return -1;
+    }
+    if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return -1; }
+    if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
+        sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, i16_storage_name(out_type), out_type);
+        return -1;
+    }
+    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, I16_TOO_LONG)) return -1;
+    if (channels == 0) return 0;
+    const int n = f->config.half_window;
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
+    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
+    if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_out, out_ld * ob, out_len * ob, channels)) {
+        sg_set_error("%s: d_in and d_out overlap (the int16-storage call does not run in place: input and output rows may not share a byte)", who);
+        return -1;
+    }
+    if (!sg1d_launch_i16) { sg_set_error("%s: the int16-storage kernels are not part of this build (object not linked)", who); return -1; }
+
+    DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    const CallShape shape = call_shape(f, variant, length);
+    const bool want_moment = takes_moment32(f, n, flags);
+    const FilterPlan *plan = plan_get(ctx, f, (shape.want_edges ? NEED_EDGES : 0u) | (want_moment ? NEED_MOMENT : 0u));
+    if (!plan) return -1;
+    const float *d_moment = (want_moment && plan->moment_terms > 0) ? plan->d_moment : nullptr;
+
+    constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
+    sg::JobI16 ji;
+    memset(&ji, 0, sizeof(ji));
+    sg::Job1D &job = ji.base;
+    job_init(job, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
+    job_set_output(job, output_part(f, shape, flags, true, rows_vector_aligned(d_out, out_ld, ob, E, shape.out_shift)), shape.want_edges ? plan->d_edges : nullptr);
+    ji.out_type = (unsigned)out_type;
+    const unsigned tpc = job.tiles_per_channel;
+    for (ChannelGroups g{channels, launch_max_channels(tpc, 2)}; g.next();) {
+        job.in = reinterpret_cast<const char *>(d_in) + g.c0 * in_ld * ib;
+        job.out = static_cast<char *>(d_out) + g.c0 * out_ld * ob;
+        job.total_tiles = (unsigned)(g.nc * tpc);
+        job.edge_items = shape.want_edges ? (unsigned)(2 * g.nc) : 0u;
+        if (sg1d_launch_i16(n, d_moment ? plan->moment_terms : 0, &ji, &plan->taps32, d_moment, grid_blocks(job.total_tiles + job.edge_items), st) != 0) return -1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Several filters on one read of 16-bit rows (savgol_apply[_valid]_multi_batch_h16): enqueue_multi's job built with enqueue_h16's storage rules, on
 // sg1d_multi_h16_kernel (sg_k1d_multi_h16.hpp).  The narrow tile and the plain summation are implied, so every output fuses: 2 or 3 outputs are one
 // launch, 4 are two launches of two, 1 is the 16-bit single call with SAVGOL_BATCH_PLAIN_SUMMATION.  The checks, in this order (the first fault wins):
@@ -1132,6 +1202,18 @@ int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, i
                                  size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
     return enqueue_h16("savgol_apply_valid_batch_h16", filter, d_in, in_type, d_out, out_type, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
+                           size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_i16("savgol_apply_batch_i16", filter, d_in, d_out, out_type, channels, length, in_ld, out_ld, FULL, static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_valid_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
+                                 size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_i16("savgol_apply_valid_batch_i16", filter, d_in, d_out, out_type, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_multi_batch_h16(const SavgolFilter *const *filters, int count, const void *d_in, int in_type, void *const *d_outs, int out_type, size_t channels,
