@@ -775,6 +775,10 @@ int savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples,
 namespace {
 const char *const kH16Who = "savgol_streambank_push_block_h16";
 const char *h16_type_name(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
+size_t h16_elem(int t) { return t == SAVGOL_HIP_F32 ? 4 : 2; }         // bytes of an element of a served type
+// the two switches of block_form (sg_stream_host.hpp), read once, as sg_bank_roll_launch reads them
+bool stream_dma_switch() { static const int v = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }(); return v != 0; }
+bool stream_moment_switch() { static const int v = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }(); return v != 0; }
 
 void h16_widen(const unsigned short *in, float *out, size_t count, bool bf, hipStream_t st)
 {
@@ -798,7 +802,7 @@ int h16_staged(SavgolStreamBank *bank, sg::DeviceCtx *ctx, const unsigned short 
     char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, kH16Who));
     if (!scratch) return -1;
     float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
-    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const size_t out_elem = h16_elem(out_type);
     long long produced = 0;
     int rc = 0;
     for (size_t done = 0; done < ticks && rc >= 0; done += chunk) {
@@ -833,7 +837,7 @@ int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_sampl
     const size_t streams = bank->streams;
     {
         // not in place, like the fp32 call; compared byte-wise, the element sizes may differ
-        const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * (out_type == SAVGOL_HIP_F32 ? 4 : 2);
+        const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * h16_elem(out_type);
         const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples), out0 = reinterpret_cast<uintptr_t>(d_out);
         if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
             sg_set_error("%s: d_samples and d_out overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of outputs may not share a byte)",
@@ -853,11 +857,9 @@ int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_sampl
     double wsum = 0.0, wabs = 0.0;
     for (int k = 0; k <= 2 * n; ++k) { wsum += (double)weights[k]; wabs += std::fabs((double)weights[k]); }
     const bool centre = fma && std::fabs(wsum) < 1e-3 * wabs;
-    static const int dma_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }();
-    static const int moment_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
     const unsigned misaligned = (unsigned)((reinterpret_cast<uintptr_t>(d_samples) | reinterpret_cast<uintptr_t>(d_out)) & 15u);
     sg::StreamMomentFit fit;
-    const sg::H16Plan plan = sg::block_plan_h16(n, fma, streams, ticks, misaligned, centre, dma_env != 0, moment_env != 0,
+    const sg::H16Plan plan = sg::block_plan_h16(n, fma, streams, ticks, misaligned, centre, stream_dma_switch(), stream_moment_switch(),
                                                 [&] { return sg::stream_moment_fit(n, weights, &fit); });
     if (plan.route == sg::H16_STAGED) return h16_staged(bank, ctx, samples, ibf, ticks, d_out, out_type, st);
 
@@ -879,8 +881,8 @@ int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_sampl
     if (plan.body) {
         sg::BankJobH16 job;
         memset(&job, 0, sizeof(job));
-        job.samples = samples; job.out = d_out; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
-        job.dt_inv = bank->dt_inv; job.centre_sum = (float)wsum; job.centre = centre ? 1 : 0;
+        job.samples = samples; job.out[0] = d_out; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
+        job.dt_inv[0] = bank->dt_inv; job.centre_sum[0] = (float)wsum; job.centre[0] = centre ? 1 : 0;
         job.in_type = (unsigned)in_type; job.out_type = (unsigned)out_type;
         if (plan.form == sg::MOMENT_TILES) covered = sg::sg_bank_dma_h16_launch_mom(n, fit, weights, job, plan.geo, plan.grid, st);
         else covered = (n <= 16 ? sg::sg_bank_dma_h16_launch_lo : sg::sg_bank_dma_h16_launch_hi)(n, fma ? 1 : 0, weights, job, plan.geo, plan.grid, st);
@@ -892,7 +894,7 @@ int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_sampl
         hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, tail_grid, dim3(256), 0, st, bank->d_ring, samples, streams, ws, bank->wp, head, ibf ? 1 : 0);
         const int first = bank_advance(bank, head);
         const int rest = h16_staged(bank, ctx, samples + head * streams, ibf, plan.body,
-                                    static_cast<char *>(d_out) + head * streams * (out_type == SAVGOL_HIP_F32 ? 4 : 2), out_type, st);
+                                    static_cast<char *>(d_out) + head * streams * h16_elem(out_type), out_type, st);
         return rest < 0 || !freed ? -1 : first + rest;
     }
     // the newest min(ticks, 2n + 1) samples, widened, into the ring; the counters once
@@ -901,7 +903,9 @@ int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_sampl
     return bank_advance(bank, ticks);
 }
 
-// ---- savgol_streambank_push_block_multi ----
+}  // extern "C"
+
+// ---- savgol_streambank_push_block_multi and savgol_streambank_push_block_multi_h16: one route, two storages ----
 namespace {
 struct MultiCall {
     sg::MultiBank bank[SAVGOL_STREAM_MULTI_MAX_BANKS];
@@ -909,178 +913,90 @@ struct MultiCall {
     sg::MultiPlan plan;
 };
 
-// every refusal of the call and of its route query, in the header's order, then the plan; false = refused (text set), nothing enqueued or changed
-bool multi_prepare(const char *who, SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks, float *const *d_outs, MultiCall *call)
-{
-    if (!banks || !d_outs || !d_samples) { sg_set_error("%s: NULL pointer", who); return false; }
-    if (count < 1 || count > SAVGOL_STREAM_MULTI_MAX_BANKS) {
-        sg_set_error("%s: count %d is outside 1..%d", who, count, SAVGOL_STREAM_MULTI_MAX_BANKS);
-        return false;
+// What the two fused calls differ in, the storage of the samples and of the outputs: the element types, the type-pair check, the texts of the overlap
+// refusals, the plan, the body's job and launchers, the tail store and the single call (SINGLE plans, and the rest of a partly refused call).
+struct FusedF32 {
+    typedef float Sample;
+    typedef float Out;
+    typedef sg::BankJobMulti Job;
+    static constexpr bool staged_head = false;               // the heads run on the caller's buffers
+    static constexpr int  in_type = SAVGOL_HIP_F32, out_type = SAVGOL_HIP_F32;
+    bool types_ok(const char *) const { return true; }
+    void samples_overlap(const char *who, int k, unsigned long long, unsigned long long) const
+    {
+        sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the two ranges of ticks x streams floats may not share a byte)", who, k);
     }
-    for (int k = 0; k < count; ++k) {
-        if (!banks[k]) { sg_set_error("%s: NULL pointer: banks[%d]", who, k); return false; }
-        if (!d_outs[k]) { sg_set_error("%s: NULL pointer: d_outs[%d]", who, k); return false; }
+    void outputs_overlap(const char *who, int j, int k, unsigned long long) const
+    {
+        sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes ticks x streams floats of its own)", who, j, k);
     }
-    for (int k = 1; k < count; ++k)
-        for (int j = 0; j < k; ++j)
-            if (banks[k] == banks[j]) { sg_set_error("%s: banks[%d] and banks[%d] are the same bank (a bank is listed twice)", who, j, k); return false; }
-    for (int k = 1; k < count; ++k)
-        if (banks[k]->streams != banks[0]->streams) {
-            sg_set_error("%s: banks[%d] has %zu streams, banks[0] has %zu (the banks of one call share the samples)", who, k, banks[k]->streams, banks[0]->streams);
-            return false;
-        }
-    for (int k = 0; k < count; ++k)
-        if (!sg::bank_on_current_device(banks[k], who)) return false;
-    if (ticks > ((size_t)1 << 30)) { sg_set_error("%s: %zu ticks in one call, more than 2^30: split the call", who, ticks); return false; }
-    const size_t streams = banks[0]->streams;
-    const unsigned long long bytes = (unsigned long long)ticks * streams * sizeof(float);
-    const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples);
-    for (int k = 0; k < count && bytes; ++k) {
-        const uintptr_t out0 = reinterpret_cast<uintptr_t>(d_outs[k]);
-        if (in0 < out0 + bytes && out0 < in0 + bytes) {
-            sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the two ranges of ticks x streams floats may not share a byte)", who, k);
-            return false;
-        }
-        for (int j = 0; j < k; ++j) {
-            const uintptr_t o = reinterpret_cast<uintptr_t>(d_outs[j]);
-            if (o < out0 + bytes && out0 < o + bytes) {
-                sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes ticks x streams floats of its own)", who, j, k);
-                return false;
-            }
-        }
+    template <class... A> static sg::MultiPlan plan(A &&...a) { return sg::block_plan_multi(static_cast<A &&>(a)...); }
+    void types_into(Job *) const {}
+    int launch(bool fma, int n, int per, const float *const *center, const Job &job, const sg::MultiPlan &plan, hipStream_t st) const
+    {
+        return (fma ? sg::sg_bank_dma_multi_launch_fma : sg::sg_bank_dma_multi_launch_ref)(n, per, center, job, plan, st);
     }
-    // the route, decided before anything is enqueued (sg_stream_host.hpp).  Centring and the two switches as sg_bank_roll_launch reads them.
-    static const int dma_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }();
-    static const int moment_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
-    uintptr_t low = in0;
-    for (int k = 0; k < count; ++k) {
-        const SavgolFilter *f = banks[k]->filter;
-        const int n = f->config.half_window;
-        const bool fma = (banks[k]->flags & SAVGOL_STREAMBANK_FMA) != 0;
-        double wsum = 0.0, wabs = 0.0;
-        for (int i = 0; i <= 2 * n; ++i) { wsum += (double)f->center_weights[i]; wabs += std::fabs((double)f->center_weights[i]); }
-        call->bank[k] = sg::MultiBank{n, fma, fma && std::fabs(wsum) < 1e-3 * wabs};
-        call->wsum[k] = (float)wsum;
-        low |= reinterpret_cast<uintptr_t>(d_outs[k]) | reinterpret_cast<uintptr_t>(banks[k]->d_ring);
+    void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t done, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(sg::sg_bank_store_tail_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
+                           b->filter->window_size, b->wp, done);
     }
-    sg::StreamMomentFit fit;
-    call->plan = sg::block_plan_multi(call->bank, count, streams, ticks, (unsigned)(low & 15u), dma_env != 0, moment_env != 0,
-                                      [&](int k) { return sg::stream_moment_fit(call->bank[k].n, banks[k]->filter->center_weights, &fit); });
-    return true;
-}
-}  // namespace
-
-int savgol_streambank_push_block_multi_route(SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks, float *const *d_outs)
-{
-    MultiCall call;
-    if (!multi_prepare("savgol_streambank_push_block_multi_route", banks, count, d_samples, ticks, d_outs, &call)) return -1;
-    return ticks == 0 ? 0 : call.plan.launches;
-}
-
-int savgol_streambank_push_block_multi(SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks, float *const *d_outs, int *produced,
-                                       void *stream)
-{
-    const char *who = "savgol_streambank_push_block_multi";
-    MultiCall call;
-    if (!multi_prepare(who, banks, count, d_samples, ticks, d_outs, &call)) return -1;
-    if (produced) for (int k = 0; k < count; ++k) produced[k] = 0;
-    if (ticks == 0) return 0;
-    int least = 0x7fffffff;
-    auto singles = [&]() -> int {                            // `count` single calls, in the caller's order
-        for (int k = 0; k < count; ++k) {
-            const int rc = savgol_streambank_push_block(banks[k], d_samples, ticks, d_outs[k], stream);
-            if (rc < 0) return -1;
-            if (produced) produced[k] = rc;
-            least = rc < least ? rc : least;
-        }
-        return least;
-    };
-    const sg::MultiPlan &plan = call.plan;
-    if (plan.launches == 0) return singles();
-
-    sg::DeviceCtx *ctx = sg::ctx_get();
-    if (!ctx) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t streams = banks[0]->streams;
-    const int n = call.bank[0].n;
-    const bool fma = call.bank[0].fma;
-    // ---- head: every bank's own tiles of bands 0 and 1, on its own ring ----
-    for (int k = 0; k < count; ++k) {
-        SavgolStreamBank *b = banks[k];
-        if (sg::sg_bank_roll_launch(n, b->filter->center_weights, b->d_ring, d_samples, d_outs[k], streams, b->wp, b->received, plan.head, b->dt_inv, fma ? 1 : 0,
-                                    ctx->cu_count, st) != 0) {
-            // nothing of bank k or the banks behind it is enqueued and no counter has moved: the heads already enqueued wrote only rows the call owns
-            sg_set_error("%s: no kernel for half_window %d", who, n);
-            return -1;
-        }
-    }
-    // ---- body: bands >= 2 of all outputs, one launch of 2 or 3, or two launches of two ----
-    int covered = 0, k0 = 0;
-    for (int l = 0; l < plan.launches && covered == 0; ++l) {
-        const int per = plan.per[l];
-        sg::BankJobMulti job;
-        memset(&job, 0, sizeof(job));
-        const float *center[sg::STREAM_MULTI_PER_LAUNCH] = {};
-        job.samples = d_samples; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(plan.head / 32);
-        for (int j = 0; j < per; ++j) {
-            const SavgolStreamBank *b = banks[k0 + j];
-            job.out[j] = d_outs[k0 + j]; job.dt_inv[j] = b->dt_inv; job.centre_sum[j] = call.wsum[k0 + j]; job.centre[j] = call.bank[k0 + j].centre ? 1 : 0;
-            center[j] = b->filter->center_weights;
-        }
-        covered = (fma ? sg::sg_bank_dma_multi_launch_fma : sg::sg_bank_dma_multi_launch_ref)(n, per, center, job, plan, st);
-        if (covered == 0) k0 += per;
-    }
-    const dim3 tail_grid((unsigned)((streams + 255) / 256), 8);
-    // ---- tail: the newest samples into every ring, the counters once per bank ----
-    int first[SAVGOL_STREAM_MULTI_MAX_BANKS] = {};
-    bool rest = false;
-    for (int k = 0; k < count; ++k) {
-        SavgolStreamBank *b = banks[k];
-        // banks whose body launch the runtime refused: the head becomes a finished 64-tick push, the rest of the call goes through single calls
-        const size_t done = k < k0 ? ticks : plan.head;
-        hipLaunchKernelGGL(sg::sg_bank_store_tail_kernel, tail_grid, dim3(256), 0, st, b->d_ring, d_samples, streams, b->filter->window_size, b->wp, done);
-        first[k] = bank_advance(b, done);
-        rest = rest || done < ticks;
-    }
-    if (!sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block_multi launch")) return -1;
-    if (rest) {
-        for (int k = 0; k < count; ++k) {
-            int all = first[k];
-            if (k >= k0) {
-                const int rc = savgol_streambank_push_block(banks[k], d_samples + plan.head * streams, plan.body, d_outs[k] + plan.head * streams, stream);
-                if (rc < 0) return -1;
-                all += rc;
-            }
-            first[k] = all;
-        }
-    }
-    for (int k = 0; k < count; ++k) {
-        if (produced) produced[k] = first[k];
-        least = first[k] < least ? first[k] : least;
-    }
-    return least;
-}
-
-// ---- savgol_streambank_push_block_multi_h16 ----
-namespace {
-// every refusal of the call and of its route query, in the header's order, then the plan; false = refused (text set), nothing enqueued or changed
-bool multi_h16_prepare(const char *who, SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks, void *const *d_outs,
-                       int out_type, MultiCall *call)
-{
-    if (!banks || !d_outs || !d_samples) { sg_set_error("%s: NULL pointer", who); return false; }
-    if (count < 1 || count > SAVGOL_STREAM_MULTI_MAX_BANKS) {
-        sg_set_error("%s: count %d is outside 1..%d", who, count, SAVGOL_STREAM_MULTI_MAX_BANKS);
-        return false;
-    }
-    for (int k = 0; k < count; ++k) {
-        if (!banks[k]) { sg_set_error("%s: NULL pointer: banks[%d]", who, k); return false; }
-        if (!d_outs[k]) { sg_set_error("%s: NULL pointer: d_outs[%d]", who, k); return false; }
-    }
-    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
+    int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, Out *out, void *stream) const { return savgol_streambank_push_block(b, samples, ticks, out, stream); }
+};
+struct FusedH16 {
+    typedef unsigned short Sample;
+    typedef void Out;
+    typedef sg::BankJobMultiH16 Job;
+    static constexpr bool staged_head = true;                // the heads run on the head's rows widened into fp32 scratch, and are rounded out
+    int in_type, out_type;
+    bool types_ok(const char *who) const
+    {
+        if ((in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16) && (out_type == in_type || out_type == SAVGOL_HIP_F32)) return true;
         sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who,
                      h16_type_name(in_type), h16_type_name(out_type), in_type, out_type);
         return false;
     }
+    void samples_overlap(const char *who, int k, unsigned long long in_bytes, unsigned long long out_bytes) const
+    {
+        sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of an output may not share a byte)",
+                     who, k, in_bytes, out_bytes);
+    }
+    void outputs_overlap(const char *who, int j, int k, unsigned long long out_bytes) const
+    {
+        sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes %llu bytes of its own)", who, j, k, out_bytes);
+    }
+    template <class... A> static sg::MultiPlan plan(A &&...a) { return sg::block_plan_multi_h16(static_cast<A &&>(a)...); }
+    void types_into(Job *job) const { job->in_type = (unsigned)in_type; job->out_type = (unsigned)out_type; }
+    int launch(bool fma, int n, int per, const float *const *center, const Job &job, const sg::MultiPlan &plan, hipStream_t st) const
+    {
+        return (fma ? sg::sg_bank_dma_multi_h16_launch_fma : sg::sg_bank_dma_multi_h16_launch_ref)(n, per, center, job, plan, st);
+    }
+    void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t done, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
+                           b->filter->window_size, b->wp, done, in_type == SAVGOL_HIP_BF16 ? 1 : 0);
+    }
+    int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, Out *out, void *stream) const
+    {
+        return savgol_streambank_push_block_h16(b, samples, in_type, ticks, out, out_type, stream);
+    }
+};
+
+// every refusal of the call and of its route query, in the header's order, then the plan; false = refused (text set), nothing enqueued or changed
+template <class S>
+bool fused_prepare(const S &store, const char *who, SavgolStreamBank *const *banks, int count, const typename S::Sample *d_samples, size_t ticks,
+                   typename S::Out *const *d_outs, MultiCall *call)
+{
+    if (!banks || !d_outs || !d_samples) { sg_set_error("%s: NULL pointer", who); return false; }
+    if (count < 1 || count > SAVGOL_STREAM_MULTI_MAX_BANKS) {
+        sg_set_error("%s: count %d is outside 1..%d", who, count, SAVGOL_STREAM_MULTI_MAX_BANKS);
+        return false;
+    }
+    for (int k = 0; k < count; ++k) {
+        if (!banks[k]) { sg_set_error("%s: NULL pointer: banks[%d]", who, k); return false; }
+        if (!d_outs[k]) { sg_set_error("%s: NULL pointer: d_outs[%d]", who, k); return false; }
+    }
+    if (!store.types_ok(who)) return false;
     for (int k = 1; k < count; ++k)
         for (int j = 0; j < k; ++j)
             if (banks[k] == banks[j]) { sg_set_error("%s: banks[%d] and banks[%d] are the same bank (a bank is listed twice)", who, j, k); return false; }
@@ -1094,26 +1010,17 @@ bool multi_h16_prepare(const char *who, SavgolStreamBank *const *banks, int coun
     if (ticks > ((size_t)1 << 30)) { sg_set_error("%s: %zu ticks in one call, more than 2^30: split the call", who, ticks); return false; }
     const size_t streams = banks[0]->streams;
     // not in place and no two outputs on one byte; compared byte-wise, the element sizes may differ
-    const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * (out_type == SAVGOL_HIP_F32 ? 4 : 2);
+    const unsigned long long in_bytes = (unsigned long long)ticks * streams * h16_elem(store.in_type), out_bytes = (unsigned long long)ticks * streams * h16_elem(store.out_type);
     const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples);
     for (int k = 0; k < count && in_bytes; ++k) {
         const uintptr_t out0 = reinterpret_cast<uintptr_t>(d_outs[k]);
-        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
-            sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of an output may not share a byte)",
-                         who, k, in_bytes, out_bytes);
-            return false;
-        }
+        if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) { store.samples_overlap(who, k, in_bytes, out_bytes); return false; }
         for (int j = 0; j < k; ++j) {
             const uintptr_t o = reinterpret_cast<uintptr_t>(d_outs[j]);
-            if (o < out0 + out_bytes && out0 < o + out_bytes) {
-                sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes %llu bytes of its own)", who, j, k, out_bytes);
-                return false;
-            }
+            if (o < out0 + out_bytes && out0 < o + out_bytes) { store.outputs_overlap(who, j, k, out_bytes); return false; }
         }
     }
     // the route, decided before anything is enqueued (sg_stream_host.hpp).  Centring and the two switches as sg_bank_roll_launch reads them.
-    static const int dma_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }();
-    static const int moment_env = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }();
     uintptr_t low = in0;
     for (int k = 0; k < count; ++k) {
         const SavgolFilter *f = banks[k]->filter;
@@ -1126,33 +1033,36 @@ bool multi_h16_prepare(const char *who, SavgolStreamBank *const *banks, int coun
         low |= reinterpret_cast<uintptr_t>(d_outs[k]) | reinterpret_cast<uintptr_t>(banks[k]->d_ring);
     }
     sg::StreamMomentFit fit;
-    call->plan = sg::block_plan_multi_h16(call->bank, count, streams, ticks, (unsigned)(low & 15u), dma_env != 0, moment_env != 0,
-                                          [&](int k) { return sg::stream_moment_fit(call->bank[k].n, banks[k]->filter->center_weights, &fit); });
+    call->plan = S::plan(call->bank, count, streams, ticks, (unsigned)(low & 15u), stream_dma_switch(), stream_moment_switch(),
+                         [&](int k) { return sg::stream_moment_fit(call->bank[k].n, banks[k]->filter->center_weights, &fit); });
     return true;
 }
-}  // namespace
 
-int savgol_streambank_push_block_multi_h16_route(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
-                                                 void *const *d_outs, int out_type)
+template <class S>
+int fused_route(const S &store, const char *who, SavgolStreamBank *const *banks, int count, const typename S::Sample *d_samples, size_t ticks,
+                typename S::Out *const *d_outs)
 {
     MultiCall call;
-    if (!multi_h16_prepare("savgol_streambank_push_block_multi_h16_route", banks, count, d_samples, in_type, ticks, d_outs, out_type, &call)) return -1;
+    if (!fused_prepare(store, who, banks, count, d_samples, ticks, d_outs, &call)) return -1;
     return ticks == 0 ? 0 : call.plan.launches;
 }
 
-int savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
-                                           void *const *d_outs, int out_type, int *produced, void *stream)
+// rows [row, ...) of an output buffer
+template <class Out> Out *out_rows(Out *out, size_t row, size_t streams, int out_type) { return reinterpret_cast<Out *>(reinterpret_cast<char *>(out) + row * streams * h16_elem(out_type)); }
+
+template <class S>
+int fused_push(const S &store, const char *who, SavgolStreamBank *const *banks, int count, const typename S::Sample *d_samples, size_t ticks,
+               typename S::Out *const *d_outs, int *produced, void *stream)
 {
-    const char *who = "savgol_streambank_push_block_multi_h16";
     MultiCall call;
-    if (!multi_h16_prepare(who, banks, count, d_samples, in_type, ticks, d_outs, out_type, &call)) return -1;
+    if (!fused_prepare(store, who, banks, count, d_samples, ticks, d_outs, &call)) return -1;
     if (produced) for (int k = 0; k < count; ++k) produced[k] = 0;
     if (ticks == 0) return 0;
     int least = 0x7fffffff;
     const sg::MultiPlan &plan = call.plan;
-    if (plan.launches == 0) {                                // `count` single 16-bit calls, in the caller's order
+    if (plan.launches == 0) {                                // `count` single calls, in the caller's order
         for (int k = 0; k < count; ++k) {
-            const int rc = savgol_streambank_push_block_h16(banks[k], d_samples, in_type, ticks, d_outs[k], out_type, stream);
+            const int rc = store.single(banks[k], d_samples, ticks, d_outs[k], stream);
             if (rc < 0) return -1;
             if (produced) produced[k] = rc;
             least = rc < least ? rc : least;
@@ -1163,70 +1073,77 @@ int savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int c
     sg::DeviceCtx *ctx = sg::ctx_get();
     if (!ctx) return -1;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned short *samples = static_cast<const unsigned short *>(d_samples);
-    const size_t streams = banks[0]->streams, out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const size_t streams = banks[0]->streams, head = plan.head;
     const int n = call.bank[0].n;
-    const bool fma = call.bank[0].fma, ibf = in_type == SAVGOL_HIP_BF16;
-    // ---- head: rows 0..63 widened once for all banks; then every bank's own fp32 tiles of bands 0 and 1 on its own ring, rounded out (the twin's own
-    // head: its silent ticks, ring reads and centring).  One allocation / free pair from the pool, the output frame reused bank after bank ----
-    const size_t head = plan.head, frame = head * streams * sizeof(float);                  // streams % 128 == 0: the second frame stays aligned
-    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, who));
-    if (!scratch) return -1;
-    float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
-    h16_widen(samples, sin, head * streams, ibf, st);
+    const bool fma = call.bank[0].fma;
+    // ---- head: every bank's own fp32 tiles of bands 0 and 1, on its own ring (the twin's own head: its silent ticks, ring reads and centring) -- on the
+    // caller's buffers, or on rows 0..63 widened once for all banks and rounded out bank after bank: one allocation / free pair from the pool, the
+    // output frame reused ----
+    char *scratch = nullptr;
+    const float *head_in = nullptr;
+    float *head_out = nullptr;
+    if constexpr (S::staged_head) {
+        const size_t frame = head * streams * sizeof(float);                                // streams % 128 == 0: the second frame stays aligned
+        scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, who));
+        if (!scratch) return -1;
+        head_in = reinterpret_cast<float *>(scratch);
+        head_out = reinterpret_cast<float *>(scratch + frame);
+        h16_widen(d_samples, reinterpret_cast<float *>(scratch), head * streams, store.in_type == SAVGOL_HIP_BF16, st);
+    } else {
+        head_in = d_samples;
+    }
     for (int k = 0; k < count; ++k) {
         SavgolStreamBank *b = banks[k];
-        if (sg::sg_bank_roll_launch(n, b->filter->center_weights, b->d_ring, sin, sout, streams, b->wp, b->received, head, b->dt_inv, fma ? 1 : 0, ctx->cu_count, st) != 0) {
+        if constexpr (!S::staged_head) head_out = d_outs[k];
+        if (sg::sg_bank_roll_launch(n, b->filter->center_weights, b->d_ring, head_in, head_out, streams, b->wp, b->received, head, b->dt_inv, fma ? 1 : 0,
+                                    ctx->cu_count, st) != 0) {
             // nothing of bank k or the banks behind it is enqueued and no counter has moved: the heads already enqueued wrote only rows the call owns
-            (void)sg::scratch_free(scratch, st, who);
+            if (scratch) (void)sg::scratch_free(scratch, st, who);
             sg_set_error("%s: no kernel for half_window %d", who, n);
             return -1;
         }
-        const unsigned long long ws = (unsigned long long)b->filter->window_size;
-        const size_t silent = b->received + 1 >= ws ? 0 : (size_t)(ws - 1 - b->received);         // head ticks without an output (<= 2n <= 64)
-        h16_round(sout, d_outs[k], streams, silent, head, out_type, st);
+        if constexpr (S::staged_head) {
+            const unsigned long long ws = (unsigned long long)b->filter->window_size;
+            const size_t silent = b->received + 1 >= ws ? 0 : (size_t)(ws - 1 - b->received);     // head ticks without an output (<= 2n <= 64)
+            h16_round(head_out, d_outs[k], streams, silent, head, store.out_type, st);
+        }
     }
-    const bool freed = sg::scratch_free(scratch, st, who);
+    const bool freed = !scratch || sg::scratch_free(scratch, st, who);
     // ---- body: bands >= 2 of all outputs, one launch of 2 or 3, or two launches of two ----
     int covered = 0, k0 = 0;
     for (int l = 0; l < plan.launches && covered == 0; ++l) {
         const int per = plan.per[l];
-        sg::BankJobMultiH16 job;
+        typename S::Job job;
         memset(&job, 0, sizeof(job));
         const float *center[sg::STREAM_MULTI_PER_LAUNCH] = {};
-        job.samples = samples; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
-        job.in_type = (unsigned)in_type; job.out_type = (unsigned)out_type;
+        job.samples = d_samples; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
+        store.types_into(&job);
         for (int j = 0; j < per; ++j) {
             const SavgolStreamBank *b = banks[k0 + j];
             job.out[j] = d_outs[k0 + j]; job.dt_inv[j] = b->dt_inv; job.centre_sum[j] = call.wsum[k0 + j]; job.centre[j] = call.bank[k0 + j].centre ? 1 : 0;
             center[j] = b->filter->center_weights;
         }
-        covered = (fma ? sg::sg_bank_dma_multi_h16_launch_fma : sg::sg_bank_dma_multi_h16_launch_ref)(n, per, center, job, plan, st);
+        covered = store.launch(fma, n, per, center, job, plan, st);
         if (covered == 0) k0 += per;
     }
-    const dim3 tail_grid((unsigned)((streams + 255) / 256), 8);
-    // ---- tail: the newest samples, widened, into every ring, the counters once per bank ----
+    // ---- tail: the newest samples into every ring, the counters once per bank ----
     int first[SAVGOL_STREAM_MULTI_MAX_BANKS] = {};
     bool rest = false;
     for (int k = 0; k < count; ++k) {
-        SavgolStreamBank *b = banks[k];
-        // banks whose body launch the runtime refused: the head becomes a finished 64-tick push, the rest of the call goes through single 16-bit calls
+        // banks whose body launch the runtime refused: the head becomes a finished 64-tick push, the rest of the call goes through single calls
         const size_t done = k < k0 ? ticks : head;
-        hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, tail_grid, dim3(256), 0, st, b->d_ring, samples, streams, b->filter->window_size, b->wp, done, ibf ? 1 : 0);
-        first[k] = bank_advance(b, done);
+        store.store_tail(banks[k], d_samples, done, st);
+        first[k] = bank_advance(banks[k], done);
         rest = rest || done < ticks;
     }
-    if (!freed || !sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block_multi_h16 launch")) return -1;
+    char what[64];
+    snprintf(what, sizeof(what), "%s launch", who);
+    if (!freed || !sg::hip_ok(hipGetLastError(), what)) return -1;
     if (rest) {
-        for (int k = 0; k < count; ++k) {
-            int all = first[k];
-            if (k >= k0) {
-                const int rc = savgol_streambank_push_block_h16(banks[k], samples + head * streams, in_type, plan.body,
-                                                                static_cast<char *>(d_outs[k]) + head * streams * out_elem, out_type, stream);
-                if (rc < 0) return -1;
-                all += rc;
-            }
-            first[k] = all;
+        for (int k = k0; k < count; ++k) {
+            const int rc = store.single(banks[k], d_samples + head * streams, plan.body, out_rows(d_outs[k], head, streams, store.out_type), stream);
+            if (rc < 0) return -1;
+            first[k] += rc;
         }
     }
     for (int k = 0; k < count; ++k) {
@@ -1234,6 +1151,34 @@ int savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int c
         least = first[k] < least ? first[k] : least;
     }
     return least;
+}
+}  // namespace
+
+extern "C" {
+
+int savgol_streambank_push_block_multi_route(SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks, float *const *d_outs)
+{
+    return fused_route(FusedF32{}, "savgol_streambank_push_block_multi_route", banks, count, d_samples, ticks, d_outs);
+}
+
+int savgol_streambank_push_block_multi(SavgolStreamBank *const *banks, int count, const float *d_samples, size_t ticks, float *const *d_outs, int *produced,
+                                       void *stream)
+{
+    return fused_push(FusedF32{}, "savgol_streambank_push_block_multi", banks, count, d_samples, ticks, d_outs, produced, stream);
+}
+
+int savgol_streambank_push_block_multi_h16_route(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
+                                                 void *const *d_outs, int out_type)
+{
+    return fused_route(FusedH16{in_type, out_type}, "savgol_streambank_push_block_multi_h16_route", banks, count, static_cast<const unsigned short *>(d_samples), ticks,
+                       d_outs);
+}
+
+int savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
+                                           void *const *d_outs, int out_type, int *produced, void *stream)
+{
+    return fused_push(FusedH16{in_type, out_type}, "savgol_streambank_push_block_multi_h16", banks, count, static_cast<const unsigned short *>(d_samples), ticks,
+                      d_outs, produced, stream);
 }
 
 static int bank_edge_rows(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream, bool leading, const char *who)

@@ -236,15 +236,8 @@ static int launch_bank_dma_mom(const StreamMomentFit &fit, const float *center, 
     // tiles of 32 ticks, (waves per block, ring pairs) = (8, 16): with a third of the arithmetic gone the block-moment tiles want FEWER resident
     // waves with deeper rings -- 8 waves per CU, 16 KiB in flight each (R5.9)
     constexpr int TRT = 32, WPB = 8, DPR = 16;
-    typedef MomGeom<N> G;
     MomTaps<N, M> taps;
-    memset(&taps, 0, sizeof(taps));
-    pack_taps(center, 8, taps.head);
-    pack_taps(center + 2 * N - 7, 8, taps.tail);
-    for (int sm = 0; sm < M; ++sm) pack_taps(fit.c[sm], G::NOFF, taps.c[sm]);
-    float q[2][8];
-    for (int t = 0; t < 8; ++t) { q[0][t] = (float)t - 3.5f; q[1][t] = q[0][t] * q[0][t] - 5.25f; }
-    for (int sm = 0; sm + 1 < M; ++sm) pack_taps(q[sm], 8, taps.q[sm]);
+    pack_mom_taps(fit, center, &taps);
     // strips per group: 32 KiB of a tick row (64 strips), a quarter of the row for narrow banks.  Measured over FRESH ALLOCATIONS inside one process
     // (tools/placement_stream.py, profiles/r05_placement_stream.txt): with 128-strip groups config 3's launch is 0.363-0.370 ms on most placements of the
     // two buffers and 0.405-0.414 on the rest (3 of 12 to 7 of 12 from call to call); with 64-strip groups 0.373-0.397 on all of them -- the same mean, a

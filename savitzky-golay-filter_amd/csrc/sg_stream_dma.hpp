@@ -1,10 +1,12 @@
-// sg_stream_dma.hpp -- device pieces shared by the LDS-DMA tile kernels of the stream block push: sg_stream_dma.hip (fp32 rows) and
-// sg_stream_dma_h16.hip (fp16 / bf16 rows): the tile shape, the counted wait, the DMA instruction, the block-moment taps.  The arithmetic of a tile -- the
-// three summation forms and the block moments -- is the fragment sg_stream_dma_feed.hpp, which both kernels' `feed` lambdas include, so the 16-bit kernel
-// computes the fp32 kernel's bits by construction.  DmaQueue and MomGeom (plain constexpr) are in sg_stream_host.hpp.
+// sg_stream_dma.hpp -- device pieces shared by the LDS-DMA tile kernels of the stream block push (sg_stream_dma.hip, sg_stream_dma_multi.hip and the body
+// tile sg_stream_dma_body.inc): the tile shape, the counted wait, the DMA instruction, the block-moment taps and their packing.  The arithmetic of a tile --
+// the three summation forms and the block moments -- is the fragment sg_stream_dma_feed.hpp, which every kernel's `feed` lambda includes, so the 16-bit and
+// fused kernels compute the fp32 kernel's bits by construction.  DmaQueue and MomGeom (plain constexpr) are in sg_stream_host.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "sg_pk.hpp"
 #include "sg_stream_roll.hpp"
@@ -40,5 +42,17 @@ template <int N, int M> struct MomTaps {
     f32x2 c[M][(MomGeom<N>::NOFF + 1) / 2];          // c[s][off]: the block at offset off = 8j - m contributes sum_s c[s][off] * moment_s
     f32x2 q[M > 1 ? M - 1 : 1][4];                   // q_s(t), s = 1 .. M - 1
 };
+// host: the bank's centre taps and the host fit of them (block_form asked for it) as a block-moment tile's kernel argument
+template <int N, int M>
+inline void pack_mom_taps(const StreamMomentFit &fit, const float *center, MomTaps<N, M> *taps)
+{
+    memset(taps, 0, sizeof(*taps));
+    pack_taps(center, 8, taps->head);
+    pack_taps(center + 2 * N - 7, 8, taps->tail);
+    for (int sm = 0; sm < M; ++sm) pack_taps(fit.c[sm], MomGeom<N>::NOFF, taps->c[sm]);
+    float q[2][8];
+    for (int t = 0; t < 8; ++t) { q[0][t] = (float)t - 3.5f; q[1][t] = q[0][t] * q[0][t] - 5.25f; }
+    for (int sm = 0; sm + 1 < M; ++sm) pack_taps(q[sm], 8, taps->q[sm]);
+}
 
 }  // namespace sg

@@ -1,15 +1,16 @@
-// sg_stream_dma_multi.hip -- savgol_streambank_push_block_multi, the body of a fused call: LDS-DMA tiles with K outputs from one read of the samples.
+// sg_stream_dma_multi.hip -- savgol_streambank_push_block_multi, the body of a fused call: LDS-DMA tiles on fp32 rows with K outputs from one read of the samples.
 //
-// sg_bank_dma_kernel (sg_stream_dma.hip) with K accumulator sets fed from ONE trip of each row through the wave's LDS ring:
-//   * a tile is the fp32 call's tile of the same band and strip -- 128 streams x 32 ticks, the twins' tile order, the same 1 KiB row pairs -- so the
-//     samples cross HBM -> LDS once for K banks: 4 + 4 K bytes per stream-tick instead of 8 K;
-//   * every arriving row is read once from the slab and fed into output k's accumulators with bank k's taps, through the fragment the fp32 kernel's
+// A body tile (bands >= 2 of a call: every row is one of the call's own rows, 2n <= 64, and every tick has an output) with its own text, because its rows
+// travel differently from the 16-bit body tile's (sg_stream_dma_body.inc; DESIGN 4.3e says why one body over both did not ship):
+//   * a tile is the fp32 call's tile of the same band and strip -- 128 streams x 32 ticks, the twins' tile order, 1 KiB row pairs (two 512-byte rows per
+//     DMA, an 8-byte LDS read per lane) -- so the samples cross HBM -> LDS once for K banks: 4 + 4 K bytes per stream-tick instead of 8 K;
+//   * every arriving row is read once from the slab and fed into output k's accumulators with bank k's taps, through the fragment every stream tile's
 //     `feed` is made of (sg_stream_dma_feed.hpp, included once per output): output k's bits are its twin's by construction;
 //   * fused bank: the sum of the tile's first eight rows is taken once out of LDS; output k runs on x - cen_k, cen_k = that centre where bank k's
 //     filter is a derivative (job.centre[k]), else 0 -- a smoothing bank and a derivative bank share a launch;
-//   * a finished output row issues K stores: DmaQueue's stores-per-row parameter (sg_stream_host.hpp; tests/mock/dma_queue_multi.cpp).
-// Only bands >= 2 of a call come here (block_plan_multi, sg_stream_host.hpp): every row is one of the call's own rows (2n <= 64) and every tick has an
-// output; rows past the call's last tick take the last row's address and finish no output, as in sg_bank_dma_h16_kernel.
+//   * a finished output row issues K stores: DmaQueue's stores-per-row parameter (sg_stream_host.hpp; tests/mock/dma_queue_multi.cpp);
+//   * rows past the call's last tick (the last band) take the last row's address and finish no output.
+// Launched through launch_body_tiles (sg_stream_dma_body.hpp), like the 16-bit body tiles.  Only bands >= 2 come here (block_plan_multi, sg_stream_host.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -19,6 +20,7 @@
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
 #include "sg_stream_dma.hpp"
+#include "sg_stream_dma_body.hpp"
 #include "sg_stream_multi.hpp"
 #include "sg_stream_roll.hpp"
 
@@ -166,16 +168,7 @@ static int launch_bank_dma_multi(const float *const *center, const BankJobMulti 
     MultiTaps<N, K> taps;
     memset(&taps, 0, sizeof(taps));
     for (int k = 0; k < K; ++k) pack_taps(center[k], SRoll<N>::WS, taps.t[k].w);
-    constexpr size_t lds = (size_t)WPB * DP * 1024;
-    static_assert(lds <= 160 * 1024, "the rings of one block must fit the CU's LDS");
-    auto kernel = sg_bank_dma_multi_kernel<N, FMA, K, 32, WPB, DP>;
-    // more than 64 KiB of dynamic LDS needs the attribute, per (function, device): set per launch, as launch_dma_tiles does
-    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return 1;
-    }
-    hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(64 * WPB), lds, st, job, taps, plan.geo);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launch_body_tiles<WPB, DP>(sg_bank_dma_multi_kernel<N, FMA, K, 32, WPB, DP>, job, taps, plan.geo, plan.grid, st);
 }
 
 // (waves per block, ring pairs) by half window, bank and output count: multi_tile_shape (sg_stream_host.hpp) as template arguments

@@ -15,14 +15,15 @@ enum : unsigned { H16_STORE_F32 = 0, H16_STORE_F16 = 1, H16_STORE_BF16 = 2 };
 
 // The body of a tile-route call: ticks band0 * 32 .. ticks - 1 of the call.  Every row a body tile reads is a 16-bit row of this call (band0 * 32 >=
 // 2n) and every tick has an output, so neither the ring nor the counters appear.  The types are wave-uniform: scalar branches at the widen and the store.
+// The per-output fields are arrays of one: the body tile (sg_stream_dma_body.inc) reads this job and BankJobMultiH16 with the same text.
 struct BankJobH16 {
     const unsigned short *samples;   // [ticks][streams], fp16 or bf16 words
-    void                 *out;       // [ticks][streams] of out_type elements
+    void                 *out[1];    // [ticks][streams] of out_type elements
     size_t                streams, ticks;          // of the whole call
     unsigned              band0;     // the twin's band of the body's first tile (2: the head is two bands)
-    float                 dt_inv;
-    float                 centre_sum;              // as BankJob's
-    int                   centre;
+    float                 dt_inv[1];
+    float                 centre_sum[1];           // as BankJob's
+    int                   centre[1];
     unsigned              in_type;   // H16_STORE_F16 or H16_STORE_BF16
     unsigned              out_type;  // the input's type, or H16_STORE_F32
 };

@@ -237,10 +237,11 @@ struct MultiPlan {
     unsigned grid;                   // ... and their grid
     int      wpb, dp;
 };
-// moment_terms(k): the host fit of bank k's taps, asked only where block_form asks
-template <class Fit>
-inline MultiPlan block_plan_multi(const MultiBank *banks, int count, size_t streams, size_t ticks, unsigned misaligned, bool dma_switch, bool moment_switch,
-                                  Fit &&moment_terms)
+// The fused plan of both storages.  What differs comes as arguments: the bound table, the (waves per block, ring in DMAs) table, and the `misaligned`
+// block_form is asked with (form_misaligned).  moment_terms(k): the host fit of bank k's taps, asked only where block_form asks
+template <class MaxN, class Shape, class Fit>
+inline MultiPlan block_plan_fused(const MultiBank *banks, int count, size_t streams, size_t ticks, unsigned misaligned, unsigned form_misaligned, bool dma_switch,
+                                  bool moment_switch, Fit &&moment_terms, MaxN &&max_n, Shape &&tile_shape)
 {
     MultiPlan plan = {};
     if (count < 2 || count > STREAM_MULTI_MAX_BANKS) return plan;
@@ -249,14 +250,14 @@ inline MultiPlan block_plan_multi(const MultiBank *banks, int count, size_t stre
     const bool fma = banks[0].fma;
     for (int k = 1; k < count; ++k)
         if (banks[k].n != n || banks[k].fma != fma) return plan;
-    if (n < 1 || n > stream_multi_max_n(fma, per0)) return plan;
+    if (n < 1 || n > max_n(fma, per0)) return plan;
     if (!tiles_take(streams, 128, misaligned, ticks, STREAM_DMA_MIN_TICKS) || ticks <= STREAM_DMA_MIN_TICKS) return plan;
     for (int k = 0; k < count; ++k)
-        if (block_form(n, fma, streams, ticks, misaligned, banks[k].centre, dma_switch, moment_switch, [&] { return moment_terms(k); }) != DMA_TILES) return plan;
+        if (block_form(n, fma, streams, ticks, form_misaligned, banks[k].centre, dma_switch, moment_switch, [&] { return moment_terms(k); }) != DMA_TILES) return plan;
     const DmaTileShape twin = dma_tile_shape(DMA_TILES, n, fma, streams);
     TileGeom whole;
     if (!tile_geom(streams, 128, ticks, 32, twin.group, twin.wpb, &whole)) return plan;      // the twin itself would leave the tiles
-    const MultiTileShape shape = multi_tile_shape(n, fma, per0);
+    const MultiTileShape shape = tile_shape(n, fma, per0);
     plan.head = STREAM_DMA_MIN_TICKS;
     plan.body = ticks - STREAM_DMA_MIN_TICKS;
     plan.wpb = shape.wpb;
@@ -267,6 +268,14 @@ inline MultiPlan block_plan_multi(const MultiBank *banks, int count, size_t stre
     plan.per[0] = per0;
     plan.per[1] = count == 4 ? 2 : 0;
     return plan;
+}
+// fp32 storage: block_form is asked with the call's own `misaligned` (the banks' heads run on the caller's buffers)
+template <class Fit>
+inline MultiPlan block_plan_multi(const MultiBank *banks, int count, size_t streams, size_t ticks, unsigned misaligned, bool dma_switch, bool moment_switch,
+                                  Fit &&moment_terms)
+{
+    return block_plan_fused(banks, count, streams, ticks, misaligned, misaligned, dma_switch, moment_switch, static_cast<Fit &&>(moment_terms), stream_multi_max_n,
+                            multi_tile_shape);
 }
 
 // ---- the fused multi-output block push on 16-bit storage (savgol_streambank_push_block_multi_h16).  Decided before anything is enqueued ----
@@ -292,36 +301,13 @@ constexpr MultiH16TileShape multi_h16_tile_shape(int n, bool fma, int outputs)
 {
     return fma && n == 6 && outputs == 2 ? MultiH16TileShape{8, 24} : MultiH16TileShape{4, 32};
 }
-// the plan is block_plan_multi's struct; dp counts DMAs of four rows
+// the plan is block_plan_multi's struct; dp counts DMAs of four rows.  block_form is asked with 0: the twin runs on aligned scratch
 template <class Fit>
 inline MultiPlan block_plan_multi_h16(const MultiBank *banks, int count, size_t streams, size_t ticks, unsigned misaligned, bool dma_switch, bool moment_switch,
                                       Fit &&moment_terms)
 {
-    MultiPlan plan = {};
-    if (count < 2 || count > STREAM_MULTI_MAX_BANKS) return plan;
-    const int per0 = count == 4 ? 2 : count;
-    const int n = banks[0].n;
-    const bool fma = banks[0].fma;
-    for (int k = 1; k < count; ++k)
-        if (banks[k].n != n || banks[k].fma != fma) return plan;
-    if (n < 1 || n > stream_multi_h16_max_n(fma, per0)) return plan;
-    if (!tiles_take(streams, 128, misaligned, ticks, STREAM_DMA_MIN_TICKS) || ticks <= STREAM_DMA_MIN_TICKS) return plan;
-    for (int k = 0; k < count; ++k)
-        if (block_form(n, fma, streams, ticks, 0u, banks[k].centre, dma_switch, moment_switch, [&] { return moment_terms(k); }) != DMA_TILES) return plan;
-    const DmaTileShape twin = dma_tile_shape(DMA_TILES, n, fma, streams);
-    TileGeom whole;
-    if (!tile_geom(streams, 128, ticks, 32, twin.group, twin.wpb, &whole)) return plan;      // the twin itself would leave the tiles
-    const MultiH16TileShape shape = multi_h16_tile_shape(n, fma, per0);
-    plan.head = STREAM_DMA_MIN_TICKS;
-    plan.body = ticks - STREAM_DMA_MIN_TICKS;
-    plan.wpb = shape.wpb;
-    plan.dp = shape.rows / 4;
-    plan.grid = tile_geom(streams, 128, plan.body, 32, twin.group, shape.wpb, &plan.geo);
-    if (!plan.grid) return plan;
-    plan.launches = count == 4 ? 2 : 1;
-    plan.per[0] = per0;
-    plan.per[1] = count == 4 ? 2 : 0;
-    return plan;
+    return block_plan_fused(banks, count, streams, ticks, misaligned, 0u, dma_switch, moment_switch, static_cast<Fit &&>(moment_terms), stream_multi_h16_max_n,
+                            [](int n, bool fma, int outputs) { const MultiH16TileShape s = multi_h16_tile_shape(n, fma, outputs); return MultiTileShape{s.wpb, s.rows / 4}; });
 }
 
 }  // namespace sg
