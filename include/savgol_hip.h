@@ -314,7 +314,8 @@ int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, i
  * channels == 0 returns 0.  Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for int16 rows, 16 for fp32
  * output) move as vectors; any other base or pitch is served element by element.  Like its siblings it only enqueues (after one warm-up call with
  * the same filter), so it can be captured into a graph.  Not served on int16: uint16 samples, a gain or offset per call or channel,
- * int16 -> fp16 / bf16 outputs, the multi-output, strided, stream-bank and 2-D calls, in place. */
+ * int16 -> fp16 / bf16 outputs, the multi-output, strided and 2-D calls, in place.  The stream bank's block push on int16:
+ * savgol_streambank_push_block_i16 below. */
 enum { SAVGOL_HIP_I16 = 3 };   /* joins SAVGOL_HIP_F32 / _F16 / _BF16 */
 int savgol_apply_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type,
                            size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
@@ -420,6 +421,32 @@ int    savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_sampl
  * type pair (named); input and output ranges that share a byte (compared byte-wise); more than 2^30 ticks (split the call); the bank on another
  * device; the tick service running.  ticks == 0 returns 0. */
 int    savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_samples, int in_type, size_t ticks,
+                                        void *d_out, int out_type, void *stream);
+/* The block push on int16 STORAGE: int16 samples (ADC / DAQ counts) in, int16 or fp32 out, fp32 arithmetic inside -- 4 bytes per stream-tick
+ * (int16 -> int16) or 6 (int16 -> fp32) instead of a widening pass, the fp32 call's 8 and a rounding pass on the caller's side.
+ * out_type is SAVGOL_HIP_I16 or SAVGOL_HIP_F32.  Rows are [tick][stream] with pitch `streams`, in elements of the buffer's own type.
+ * The bank is an ordinary bank: its ring stays fp32 and holds the samples widened exactly, so this call mixes freely with _push, _push_full, the
+ * fp32 and 16-bit float block pushes, both flushes, _save / _load and the tick service.
+ * CONTRACT: savgol_streambank_push_block_h16's with the int16 conversions of savgol_apply_batch_i16.  Let the twin be a bank of the same
+ * configuration, flags and history that takes savgol_streambank_push_block on the samples widened exactly to fp32, in 16-byte aligned fp32 buffers.
+ * For out_type F32 every output row is the twin's row bit for bit (NaN positions coincide, NaN payloads are free).  For out_type I16 every output
+ * row is the twin's row converted ONCE: rounded to nearest, ties to even; saturated to [-32768, 32767], so +-Inf saturate; NaN gives 0 (a NaN or an
+ * Inf can only come out of ring history that fp32 pushes put there).  Rows of ticks without an output are not written.  Afterwards counters, write
+ * position and ring are the twin's: the savgol_streambank_save blobs are equal byte for byte.  The return value is savgol_streambank_push_block's.
+ * None of this depends on the alignment of the int16 buffers.  The 16-bit float call's one exception carries over unchanged: the twin of a chunked
+ * staged call is the same sequence of fp32 block pushes, chunk by chunk.
+ * The two routes are savgol_streambank_push_block_h16's, chosen by the same plan before anything is enqueued.  TILES -- streams % 128 == 0,
+ * ticks >= 64, both bases 16-byte aligned, and the twin takes its LDS-DMA or block-moment tiles: the first 64 ticks are widened into fp32 scratch,
+ * go through the fp32 tiles and are converted out, the rest goes through the same tiles reading int16 rows (csrc/sg_stream_dma_i16.hip).
+ * STAGED -- every other call, in the same chunks: one piece up to 2^24 stream-ticks, else max(64, (2^24 / streams) & ~63) ticks.
+ * Returns -1 with a text naming the call, before any launch or scratch allocation, counters and ring untouched; the checks run in this order and
+ * the first fault wins:
+ *   1. a NULL pointer;   2. an out_type other than SAVGOL_HIP_I16 / SAVGOL_HIP_F32 (named);   3. the tick service running, or the bank on another
+ *   device;   4. ticks == 0 returns 0;   5. more than 2^30 ticks (split the call);   6. input and output ranges that share a byte (compared
+ *   byte-wise: the element sizes may differ; in place is not served).
+ * Not served on int16 here: uint16 samples, a gain or offset per call or stream, int16 -> fp16 / bf16 outputs, int16 in _push, _push_full, the
+ * flushes and the tick service, the fused multi-output push (savgol_streambank_push_block_multi_h16 keeps refusing SAVGOL_HIP_I16). */
+int    savgol_streambank_push_block_i16(SavgolStreamBank *bank, const int16_t *d_samples, size_t ticks,
                                         void *d_out, int out_type, void *stream);
 /* The FUSED MULTI-OUTPUT block push: `count` banks (1..4) take the same block of samples, which is read from memory once -- value, velocity and
  * acceleration of the same sensor streams move 4 + 4 * count bytes per stream-tick instead of 8 * count.

@@ -154,6 +154,7 @@ SIGNATURES = {
     "savgol_streambank_push_full": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "savgol_streambank_push_block": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "savgol_streambank_push_block_h16": (C.c_int, [_vp, _vp, C.c_int, _sz, _vp, C.c_int, _vp]),
+    "savgol_streambank_push_block_i16": (C.c_int, [_vp, _vp, _sz, _vp, C.c_int, _vp]),
     "savgol_streambank_push_block_multi": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, C.POINTER(C.c_int), _vp]),
     "savgol_streambank_push_block_multi_route": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp]),
     "savgol_streambank_push_block_multi_h16": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _sz, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
@@ -542,6 +543,14 @@ class StreamBank:
         if dtype not in _STORAGE or out_dtype not in _STORAGE:
             raise ValueError(f"push_block_h16: dtype {dtype!r} -> {out_dtype!r}")
         return lib().savgol_streambank_push_block_h16(self.ptr, _addr(samples), _STORAGE[dtype], ticks, _addr(out), _STORAGE[out_dtype], _stream(stream))
+
+    def push_block_i16(self, samples, ticks, out, out_dtype="i16", stream=None):
+        """savgol_streambank_push_block_i16: `ticks` rows of int16 samples, outputs of out_dtype ("i16" or "f32"); the fp32 block push's results on
+        the widened samples, for "i16" converted once: rounded to nearest even, saturated to [-32768, 32767], NaN gives 0"""
+        types = {"i16": SAVGOL_HIP_I16, "f32": SAVGOL_HIP_F32}
+        if out_dtype not in types:
+            raise ValueError(f"push_block_i16: out_dtype {out_dtype!r} (\"i16\" or \"f32\")")
+        return lib().savgol_streambank_push_block_i16(self.ptr, _addr(samples), ticks, _addr(out), types[out_dtype], _stream(stream))
 
     def service_start(self, idle_ms=0):
         if lib().savgol_streambank_service_start(self.ptr, idle_ms) != 0:

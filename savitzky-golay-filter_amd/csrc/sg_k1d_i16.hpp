@@ -17,38 +17,13 @@
 // kernel per half window for both outputs.
 #pragma once
 
+#include "sg_i16.hpp"
 #include "sg_k1d.hpp"
 #include "sg_k1d_i16_host.hpp"
 
 namespace sg {
 
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-typedef short i16x4 __attribute__((ext_vector_type(4)));
-
-// four int16 elements as loaded (element 0 in the low half of .x) -> fp32, exactly
-__device__ __forceinline__ float4 widen4_i16(const u32x2 raw)
-{
-    const i16x4 h = __builtin_bit_cast(i16x4, raw);
-    return float4{(float)h.x, (float)h.y, (float)h.z, (float)h.w};
-}
-// fp32 -> int32 with the HARDWARE's convert semantics, which a C++ cast does not promise: NaN gives 0, values beyond the int32 range (+-Inf
-// included) saturate.  The argument is already an integer value (rint_i16 below), so the instruction's truncation does not round.
-__device__ __forceinline__ int cvt_i32_sat(const float v)
-{
-    int r;
-    asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
-// fp32 -> the int32 the int16 output is packed from: round to nearest, ties to even, then the saturating convert
-__device__ __forceinline__ int rint_i32(const float v) { return cvt_i32_sat(__builtin_rintf(v)); }
-// two int32 -> two int16 in one dword, each saturated to [-32768, 32767] (v_cvt_pk_i16_i32); `lo` in the low half
-__device__ __forceinline__ unsigned pack2_i16(const int lo, const int hi) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(lo, hi)); }
-// fp32 -> int16: round to nearest even, saturate to [-32768, 32767] (so +-Inf saturate), NaN gives 0
-__device__ __forceinline__ u32x2 narrow4_i16(const float4 v)
-{
-    return u32x2{pack2_i16(rint_i32(v.x), rint_i32(v.y)), pack2_i16(rint_i32(v.z), rint_i32(v.w))};
-}
-__device__ __forceinline__ short narrow1_i16(const float v) { return (short)(pack2_i16(rint_i32(v), 0) & 0xffffu); }
+// the converts (widen4_i16, narrow4_i16, narrow1_i16 and what they are made of): sg_i16.hpp, shared with the stream kernels on int16 storage
 
 // int16 rows for stage_tile / store_tile (SameStorage's counterpart): a slab vector's four samples are 8 bytes of the row
 struct I16Storage {

@@ -31,8 +31,10 @@
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
 #include "sg_h16.hpp"
+#include "sg_i16.hpp"
 #include "sg_stream.hpp"
 #include "sg_stream_h16.hpp"
+#include "sg_stream_i16.hpp"
 #include "sg_stream_multi.hpp"
 #include "sg_stream_multi_h16.hpp"
 #include "sg_stream_roll.hpp"
@@ -214,6 +216,52 @@ __global__ __launch_bounds__(256) void sg_bank_store_tail_h16_kernel(float *__re
     const size_t first = ticks > (size_t)ws ? ticks - (size_t)ws : 0;
     for (size_t q = first + blockIdx.y; q < ticks; q += gridDim.y)
         ring[(size_t)((wp0 + q) % (size_t)ws) * streams + s] = widen1(samples[q * streams + s], bf != 0);
+}
+
+// ---- the block push on int16 storage (savgol_streambank_push_block_i16): the same three small kernels on int16 elements (sg_i16.hpp) ----
+// The vector / element-wise split is the 16-bit float kernels': 8-byte alignment on the 16-bit side, any base, any length.
+// int16 elements [0, count) -> fp32, exactly
+__global__ __launch_bounds__(256) void sg_i16_widen_kernel(const short *__restrict__ in, float *__restrict__ out, size_t count)
+{
+    const size_t j = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (j >= count) return;
+    if (j + 4 <= count && ((reinterpret_cast<uintptr_t>(in) & 7u) | (reinterpret_cast<uintptr_t>(out) & 15u)) == 0) {
+        const float4 v = widen4_i16(*reinterpret_cast<const u32x2 *>(in + j));
+        *reinterpret_cast<f32x4 *>(out + j) = f32x4{v.x, v.y, v.z, v.w};
+        return;
+    }
+    for (size_t i = j; i < count && i < j + 4; ++i) out[i] = (float)in[i];
+}
+// fp32 elements [lo, hi) -> int16, converted once (nearest even, saturated, NaN gives 0), or fp32 copied; elements outside the range -- rows of ticks
+// without an output -- are not written
+__global__ __launch_bounds__(256) void sg_i16_round_kernel(const float *__restrict__ in, void *__restrict__ out, size_t lo, size_t hi, int of32)
+{
+    const size_t j = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4 + (lo & ~(size_t)3);
+    if (j >= hi) return;
+    const bool whole = j >= lo && j + 4 <= hi && (reinterpret_cast<uintptr_t>(in) & 15u) == 0;
+    if (of32) {
+        float *o = static_cast<float *>(out);
+        if (whole && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) { *reinterpret_cast<f32x4 *>(o + j) = *reinterpret_cast<const f32x4 *>(in + j); return; }
+        for (size_t i = j < lo ? lo : j; i < hi && i < j + 4; ++i) o[i] = in[i];
+        return;
+    }
+    short *o = static_cast<short *>(out);
+    if (whole && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(in + j);
+        *reinterpret_cast<u32x2 *>(o + j) = u32x2{narrow2_i16(f32x2{v.x, v.y}), narrow2_i16(f32x2{v.z, v.w})};
+        return;
+    }
+    for (size_t i = j < lo ? lo : j; i < hi && i < j + 4; ++i) o[i] = narrow1_i16(in[i]);
+}
+// sg_bank_store_tail_kernel reading int16 samples: the ring stays fp32, holding the samples widened exactly
+__global__ __launch_bounds__(256) void sg_bank_store_tail_i16_kernel(float *__restrict__ ring, const short *__restrict__ samples,
+                                                                     size_t streams, int ws, int wp0, size_t ticks)
+{
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= streams) return;
+    const size_t first = ticks > (size_t)ws ? ticks - (size_t)ws : 0;
+    for (size_t q = first + blockIdx.y; q < ticks; q += gridDim.y)
+        ring[(size_t)((wp0 + q) % (size_t)ws) * streams + s] = (float)samples[q * streams + s];
 }
 
 // One tick with every load in flight at once: half window known at compile time, so the 2n ring rows a stream needs
@@ -771,9 +819,10 @@ int savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples,
     return bank_advance(bank, ticks);
 }
 
-// ---- savgol_streambank_push_block_h16 ----
+}  // extern "C"
+
+// ---- savgol_streambank_push_block_h16 and savgol_streambank_push_block_i16: one route, two storages ----
 namespace {
-const char *const kH16Who = "savgol_streambank_push_block_h16";
 const char *h16_type_name(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
 size_t h16_elem(int t) { return t == SAVGOL_HIP_F32 ? 4 : 2; }         // bytes of an element of a served type
 // the two switches of block_form (sg_stream_host.hpp), read once, as sg_bank_roll_launch reads them
@@ -793,63 +842,134 @@ void h16_round(const float *in, void *out, size_t streams, size_t first_row, siz
     hipLaunchKernelGGL(sg::sg_h16_round_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, in, out, lo, hi, out_type);
 }
 
+void i16_widen(const short *in, float *out, size_t count, hipStream_t st)
+{
+    hipLaunchKernelGGL(sg::sg_i16_widen_kernel, dim3((unsigned)((count + 1023) / 1024)), dim3(256), 0, st, in, out, count);
+}
+void i16_round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, int out_type, hipStream_t st)
+{
+    const size_t lo = first_row * streams, hi = rows * streams;
+    if (lo >= hi) return;
+    const size_t groups = (hi - (lo & ~(size_t)3) + 3) / 4;
+    hipLaunchKernelGGL(sg::sg_i16_round_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, in, out, lo, hi, out_type == SAVGOL_HIP_F32 ? 1 : 0);
+}
+
+// What the two calls differ in, the storage of the samples and of the outputs: the call's name, the type check and its text, the element sizes, the
+// widen, round and tail-store launchers, and the three launchers of the body tile.  The job is BankJobH16 for both (16-bit words either way).
+struct BlockH16 {
+    typedef unsigned short Sample;
+    static constexpr const char *who = "savgol_streambank_push_block_h16", *launch_who = "savgol_streambank_push_block_h16 launch";
+    int in_type, out_type;
+    bool types_ok() const
+    {
+        if ((in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16) && (out_type == in_type || out_type == SAVGOL_HIP_F32)) return true;
+        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who,
+                     h16_type_name(in_type), h16_type_name(out_type), in_type, out_type);
+        return false;
+    }
+    size_t out_elem() const { return h16_elem(out_type); }
+    void widen(const Sample *in, float *out, size_t count, hipStream_t st) const { h16_widen(in, out, count, in_type == SAVGOL_HIP_BF16, st); }
+    void round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { h16_round(in, out, streams, first_row, rows, out_type, st); }
+    void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t ticks, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
+                           b->filter->window_size, b->wp, ticks, in_type == SAVGOL_HIP_BF16 ? 1 : 0);
+    }
+    int launch_mom(int n, const sg::StreamMomentFit &fit, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
+    {
+        return sg::sg_bank_dma_h16_launch_mom(n, fit, center, job, geo, grid, st);
+    }
+    int launch_taps(int n, int fma, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
+    {
+        return (n <= 16 ? sg::sg_bank_dma_h16_launch_lo : sg::sg_bank_dma_h16_launch_hi)(n, fma, center, job, geo, grid, st);
+    }
+};
+struct BlockI16 {
+    typedef short Sample;
+    static constexpr const char *who = "savgol_streambank_push_block_i16", *launch_who = "savgol_streambank_push_block_i16 launch";
+    static constexpr int in_type = SAVGOL_HIP_I16;
+    int out_type;
+    bool types_ok() const
+    {
+        if (out_type == SAVGOL_HIP_I16 || out_type == SAVGOL_HIP_F32) return true;
+        sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, h16_type_name(out_type), out_type);
+        return false;
+    }
+    size_t out_elem() const { return out_type == SAVGOL_HIP_F32 ? 4 : 2; }
+    void widen(const Sample *in, float *out, size_t count, hipStream_t st) const { i16_widen(in, out, count, st); }
+    void round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { i16_round(in, out, streams, first_row, rows, out_type, st); }
+    void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t ticks, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(sg::sg_bank_store_tail_i16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
+                           b->filter->window_size, b->wp, ticks);
+    }
+    int launch_mom(int n, const sg::StreamMomentFit &fit, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
+    {
+        return sg::sg_bank_dma_i16_launch_mom(n, fit, center, job, geo, grid, st);
+    }
+    int launch_taps(int n, int fma, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
+    {
+        return (n <= 16 ? sg::sg_bank_dma_i16_launch_lo : sg::sg_bank_dma_i16_launch_hi)(n, fma, center, job, geo, grid, st);
+    }
+};
+
 // The staged route: chunk by chunk, widened into fp32 scratch, the fp32 block push (which keeps ring and counters), rounded out.  Returns the outputs
 // produced, -1 on error (text set).  The rows are those of the caller's buffers from row 0 of `d_samples` / `d_out`.
-int h16_staged(SavgolStreamBank *bank, sg::DeviceCtx *ctx, const unsigned short *d_samples, bool ibf, size_t ticks, void *d_out, int out_type, hipStream_t st)
+template <class S>
+int block16_staged(const S &store, SavgolStreamBank *bank, sg::DeviceCtx *ctx, const typename S::Sample *d_samples, size_t ticks, void *d_out, hipStream_t st)
 {
     const size_t streams = bank->streams, chunk = sg::h16_staged_chunk(streams, ticks);
     const size_t frame = (chunk * streams * sizeof(float) + 255) & ~(size_t)255;
-    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, kH16Who));
+    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, S::who));
     if (!scratch) return -1;
     float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
-    const size_t out_elem = h16_elem(out_type);
+    const size_t out_elem = store.out_elem();
     long long produced = 0;
     int rc = 0;
     for (size_t done = 0; done < ticks && rc >= 0; done += chunk) {
         const size_t part = ticks - done < chunk ? ticks - done : chunk;
-        h16_widen(d_samples + done * streams, sin, part * streams, ibf, st);
+        store.widen(d_samples + done * streams, sin, part * streams, st);
         rc = savgol_streambank_push_block(bank, sin, part, sout, st);
         if (rc < 0) break;
-        h16_round(sout, static_cast<char *>(d_out) + done * streams * out_elem, streams, part - (size_t)rc, part, out_type, st);
+        store.round(sout, static_cast<char *>(d_out) + done * streams * out_elem, streams, part - (size_t)rc, part, st);
         produced += rc;
     }
-    const bool freed = sg::scratch_free(scratch, st, kH16Who);
+    const bool freed = sg::scratch_free(scratch, st, S::who);
     if (rc < 0 || !freed) return -1;
-    if (!sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block_h16 launch")) return -1;
+    if (!sg::hip_ok(hipGetLastError(), S::launch_who)) return -1;
     return (int)produced;
 }
-}  // namespace
 
-int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_samples, int in_type, size_t ticks, void *d_out, int out_type, void *stream)
+// Both entry points: the refusals in the header's order, the plan (block_plan_h16 knows only that an element is two bytes), then the staged route or
+// the tile route -- head (two bands through the fp32 tiles), body (the tiles on 16-bit rows), tail store
+template <class S>
+int block16_push(const S &store, SavgolStreamBank *bank, const void *d_samples, size_t ticks, void *d_out, void *stream)
 {
-    if (!bank || !d_samples || !d_out) { sg_set_error("%s: NULL pointer", kH16Who); return -1; }
-    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
-        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", kH16Who,
-                     h16_type_name(in_type), h16_type_name(out_type), in_type, out_type);
-        return -1;
-    }
-    if (!sg::bank_on_current_device(bank, kH16Who)) return -1;          // the tick service running, or the bank on another device
+    const char *const who = S::who;
+    if (!bank || !d_samples || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (!store.types_ok()) return -1;
+    if (!sg::bank_on_current_device(bank, who)) return -1;              // the tick service running, or the bank on another device
     if (ticks == 0) return 0;
     if (ticks > ((size_t)1 << 30)) {
-        sg_set_error("%s: %zu ticks in one call, more than 2^30: split the call", kH16Who, ticks);
+        sg_set_error("%s: %zu ticks in one call, more than 2^30: split the call", who, ticks);
         return -1;
     }
     const size_t streams = bank->streams;
     {
         // not in place, like the fp32 call; compared byte-wise, the element sizes may differ
-        const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * h16_elem(out_type);
+        const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * store.out_elem();
         const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples), out0 = reinterpret_cast<uintptr_t>(d_out);
         if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
             sg_set_error("%s: d_samples and d_out overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of outputs may not share a byte)",
-                         kH16Who, in_bytes, out_bytes);
+                         who, in_bytes, out_bytes);
             return -1;
         }
     }
     sg::DeviceCtx *ctx = sg::ctx_get();
     if (!ctx) return -1;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned short *samples = static_cast<const unsigned short *>(d_samples);
-    const bool ibf = in_type == SAVGOL_HIP_BF16, fma = (bank->flags & SAVGOL_STREAMBANK_FMA) != 0;
+    const typename S::Sample *samples = static_cast<const typename S::Sample *>(d_samples);
+    const bool fma = (bank->flags & SAVGOL_STREAMBANK_FMA) != 0;
     const int n = bank->filter->config.half_window, ws = bank->filter->window_size;
     const float *weights = bank->filter->center_weights;
 
@@ -861,46 +981,57 @@ int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_sampl
     sg::StreamMomentFit fit;
     const sg::H16Plan plan = sg::block_plan_h16(n, fma, streams, ticks, misaligned, centre, stream_dma_switch(), stream_moment_switch(),
                                                 [&] { return sg::stream_moment_fit(n, weights, &fit); });
-    if (plan.route == sg::H16_STAGED) return h16_staged(bank, ctx, samples, ibf, ticks, d_out, out_type, st);
+    if (plan.route == sg::H16_STAGED) return block16_staged(store, bank, ctx, samples, ticks, d_out, st);
 
     // ---- the tile route: head (two bands through the fp32 tiles), body (the 16-bit tiles), tail store ----
     const size_t head = plan.head, frame = head * streams * sizeof(float);                  // streams % 128 == 0: the second frame stays aligned
-    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, kH16Who));
+    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, who));
     if (!scratch) return -1;
     float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
-    h16_widen(samples, sin, head * streams, ibf, st);
+    store.widen(samples, sin, head * streams, st);
     if (sg::sg_bank_roll_launch(n, weights, bank->d_ring, sin, sout, streams, bank->wp, bank->received, head, bank->dt_inv, fma ? 1 : 0, ctx->cu_count, st) != 0) {
-        (void)sg::scratch_free(scratch, st, kH16Who);
-        sg_set_error("%s: no kernel for half_window %d", kH16Who, n);
+        (void)sg::scratch_free(scratch, st, who);
+        sg_set_error("%s: no kernel for half_window %d", who, n);
         return -1;
     }
     const size_t silent = bank->received + 1 >= (unsigned long long)ws ? 0 : (size_t)((unsigned long long)ws - 1 - bank->received);      // head ticks without an output (<= 2n <= 64)
-    h16_round(sout, d_out, streams, silent, head, out_type, st);
-    const bool freed = sg::scratch_free(scratch, st, kH16Who);
+    store.round(sout, d_out, streams, silent, head, st);
+    const bool freed = sg::scratch_free(scratch, st, who);
     int covered = 0;
     if (plan.body) {
         sg::BankJobH16 job;
         memset(&job, 0, sizeof(job));
-        job.samples = samples; job.out[0] = d_out; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
+        job.samples = reinterpret_cast<const unsigned short *>(samples); job.out[0] = d_out; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
         job.dt_inv[0] = bank->dt_inv; job.centre_sum[0] = (float)wsum; job.centre[0] = centre ? 1 : 0;
-        job.in_type = (unsigned)in_type; job.out_type = (unsigned)out_type;
-        if (plan.form == sg::MOMENT_TILES) covered = sg::sg_bank_dma_h16_launch_mom(n, fit, weights, job, plan.geo, plan.grid, st);
-        else covered = (n <= 16 ? sg::sg_bank_dma_h16_launch_lo : sg::sg_bank_dma_h16_launch_hi)(n, fma ? 1 : 0, weights, job, plan.geo, plan.grid, st);
+        job.in_type = (unsigned)store.in_type; job.out_type = (unsigned)store.out_type;
+        if (plan.form == sg::MOMENT_TILES) covered = store.launch_mom(n, fit, weights, job, plan.geo, plan.grid, st);
+        else covered = store.launch_taps(n, fma ? 1 : 0, weights, job, plan.geo, plan.grid, st);
     }
-    const dim3 tail_grid((unsigned)((streams + 255) / 256), 8);
     if (covered != 0) {
         // the runtime refused the body's launch (nothing of the body is enqueued): the head becomes a finished block push of its own -- its newest
         // samples into the ring, the counters -- and the rest of the call takes the staged route
-        hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, tail_grid, dim3(256), 0, st, bank->d_ring, samples, streams, ws, bank->wp, head, ibf ? 1 : 0);
+        store.store_tail(bank, samples, head, st);
         const int first = bank_advance(bank, head);
-        const int rest = h16_staged(bank, ctx, samples + head * streams, ibf, plan.body,
-                                    static_cast<char *>(d_out) + head * streams * h16_elem(out_type), out_type, st);
+        const int rest = block16_staged(store, bank, ctx, samples + head * streams, plan.body, static_cast<char *>(d_out) + head * streams * store.out_elem(), st);
         return rest < 0 || !freed ? -1 : first + rest;
     }
     // the newest min(ticks, 2n + 1) samples, widened, into the ring; the counters once
-    hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, tail_grid, dim3(256), 0, st, bank->d_ring, samples, streams, ws, bank->wp, ticks, ibf ? 1 : 0);
-    if (!freed || !sg::hip_ok(hipGetLastError(), "savgol_streambank_push_block_h16 launch")) return -1;
+    store.store_tail(bank, samples, ticks, st);
+    if (!freed || !sg::hip_ok(hipGetLastError(), S::launch_who)) return -1;
     return bank_advance(bank, ticks);
+}
+}  // namespace
+
+extern "C" {
+
+int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_samples, int in_type, size_t ticks, void *d_out, int out_type, void *stream)
+{
+    return block16_push(BlockH16{in_type, out_type}, bank, d_samples, ticks, d_out, stream);
+}
+
+int savgol_streambank_push_block_i16(SavgolStreamBank *bank, const int16_t *d_samples, size_t ticks, void *d_out, int out_type, void *stream)
+{
+    return block16_push(BlockI16{out_type}, bank, d_samples, ticks, d_out, stream);
 }
 
 }  // extern "C"

@@ -22,6 +22,11 @@
 //   * a finished output row issues K stores (DmaQueue<N, 32, DP, 4, K>, sg_stream_host.hpp; tests/mock/dma_queue_multi_h16.cpp): 16 -> 16 bit rounds the
 //     pair once to nearest even into one dword, 16 bit -> fp32 keeps the fp32 store; range-checked descriptors, nontemporal like the fp32 tile's.
 // The block-moment form (MOM > 0) is the single call's (K = 1) alone.
+// STORAGE, a compile-time switch of the including file: with SG_BODY_I16 defined before the #include the 16-bit rows are int16 (sg_bank_dma_i16_kernel,
+// sg_stream_dma_i16.hip; sg_i16.hpp) -- the widen is the exact sign-extending convert of the dword's two halves and a 16-bit output row is rounded to
+// nearest even, saturated and packed once (NaN gives 0); in_type / out_type then only tell a 16-bit output row from an fp32 one, and the output step asks for
+// the 16-bit store first (the same two stores, one per output row).  Without it the three places below read what they always did: fp16 / bf16 by the
+// job's wave-uniform types (sg_h16.hpp).
     typedef DmaQueue<N, TRT, DP, 4, K> Q;
     constexpr int TR = TRT, ROWS = TR + 2 * N, NI = Q::NI, RB = 256, RING = DP * 1024;
     static_assert(DP >= 2 && DP <= NI, "ring of row quads; the first eight rows are in it together");
@@ -87,6 +92,17 @@
             const f32x2 y = (MOM > 0 || FMA) ? __builtin_elementwise_fma(a, f32x2{job.dt_inv[k], job.dt_inv[k]}, backdts[k]) : a * f32x2{job.dt_inv[k], job.dt_inv[k]};
             const size_t orow = (size_t)(has_out ? tt : 0) * job.streams;
             // one store per output and output row whatever the type (the queue arithmetic is static); a row past the call stores into an empty descriptor
+#ifdef SG_BODY_I16
+            // the same two stores with the 16-bit one asked for first: in that order the int16 narrow (two temporaries where the bf16 convert needs one)
+            // does not sit at the tile's register peak (DESIGN 4.3f)
+            if (!of32) {
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 2) : 0, 0x00020000);
+                __builtin_amdgcn_raw_buffer_store_b32(narrow2_i16(y), rs, (int)(voff * 2u), 0, 2);
+            } else {
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<float *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 4) : 0, 0x00020000);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)(voff * 4u), 0, 2);
+            }
+#else
             if (of32) {
                 const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<float *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 4) : 0, 0x00020000);
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)(voff * 4u), 0, 2);
@@ -94,6 +110,7 @@
                 const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 2) : 0, 0x00020000);
                 __builtin_amdgcn_raw_buffer_store_b32(narrow2(y, obf), rs, (int)(voff * 2u), 0, 2);
             }
+#endif
         }
     };
     // the centre of the centred outputs: the sum of the tile's first eight widened rows (all real samples here), once, out of LDS after two DMAs have landed
@@ -103,7 +120,11 @@
         if (any) {
             f32x2 sum = f32x2{0.0f, 0.0f};
             wait_vm<(Q::younger(1, 0) > 63 ? 63 : Q::younger(1, 0))>();
+#ifdef SG_BODY_I16
+            static_for<8>([&](auto rc) -> bool { sum = sum + widen2_i16(row_in(rc)); return true; });
+#else
             static_for<8>([&](auto rc) -> bool { sum = sum + widen2(row_in(rc), ibf); return true; });
+#endif
             const f32x2 cen = centre_guard(sum);
             static_for<K>([&](auto kc) -> bool {
                 constexpr int k = decltype(kc)::value;
@@ -135,7 +156,11 @@
         auto take = [&](auto rc, const unsigned raw) {
             constexpr int r = decltype(rc)::value;
             if constexpr (r < ROWS) {                                                             // pad rows are never fed
+#ifdef SG_BODY_I16
+                const f32x2 wide = widen2_i16(raw);                                               // once per row, for every output
+#else
                 const f32x2 wide = widen2(raw, ibf);                                              // once per row, for every output
+#endif
                 static_for<K>([&](auto kc) -> bool {
                     if constexpr (MOM > 0 || FMA) feed(kc, rc, wide - cens[decltype(kc)::value]);
                     else feed(kc, rc, wide);
