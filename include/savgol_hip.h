@@ -27,6 +27,8 @@
  *     of the staged route's chunk); capturable after one warm-up call like savgol_streambank_push_block;
  *   - savgol_streambank_push_block_multi_h16: a fused call makes launches plus ONE such pair (the two fp32 frames of its head, shared by the banks);
  *     a call that falls back is `count` savgol_streambank_push_block_h16 calls; capturable after one warm-up call;
+ *   - savgol_streambank_push_block_multi_i16: the same on int16 samples -- a fused call makes launches plus ONE such pair; a call that falls back is
+ *     `count` savgol_streambank_push_block_i16 calls; capturable after one warm-up call;
  *   - savgol_streambank_save/_load, savgol_hip_synchronize and every host-pointer drop-in call of savgolFilter.h /
  *     savgol_stream.h / savgol2d.h: synchronous by nature (they return host data).
  * Short host-pointer calls (savgol_apply / _valid / _strided on <= 4096 samples and <= 64 K multiply-adds, every savgol_stream_* call
@@ -445,7 +447,8 @@ int    savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_sa
  *   device;   4. ticks == 0 returns 0;   5. more than 2^30 ticks (split the call);   6. input and output ranges that share a byte (compared
  *   byte-wise: the element sizes may differ; in place is not served).
  * Not served on int16 here: uint16 samples, a gain or offset per call or stream, int16 -> fp16 / bf16 outputs, int16 in _push, _push_full, the
- * flushes and the tick service, the fused multi-output push (savgol_streambank_push_block_multi_h16 keeps refusing SAVGOL_HIP_I16). */
+ * flushes and the tick service.  The fused multi-output push on int16 is savgol_streambank_push_block_multi_i16 below
+ * (savgol_streambank_push_block_multi_h16 keeps refusing SAVGOL_HIP_I16). */
 int    savgol_streambank_push_block_i16(SavgolStreamBank *bank, const int16_t *d_samples, size_t ticks,
                                         void *d_out, int out_type, void *stream);
 /* The FUSED MULTI-OUTPUT block push: `count` banks (1..4) take the same block of samples, which is read from memory once -- value, velocity and
@@ -503,6 +506,38 @@ int    savgol_streambank_push_block_multi_route(SavgolStreamBank *const *banks, 
 int    savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
                                               void *const *d_outs, int out_type, int *produced, void *stream);
 int    savgol_streambank_push_block_multi_h16_route(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
+                                                    void *const *d_outs, int out_type);
+/* The FUSED MULTI-OUTPUT block push on int16 STORAGE: `count` banks (1..4) take the same block of int16 samples (ADC / DAQ counts), which is read
+ * from memory once, and write int16 or fp32 outputs: value, velocity and acceleration of the same sensor streams move 2 + 2 * count bytes per
+ * stream-tick (int16 -> int16) instead of 4 * count, or 2 + 4 * count (int16 -> fp32) instead of 6 * count.
+ * `banks` and `d_outs` are host arrays of `count` entries; the banks are ordinary banks (fp32 rings), all with the same `streams`.  out_type is
+ * SAVGOL_HIP_I16 or SAVGOL_HIP_F32, ONE output type for every output.  d_samples is one block [ticks][streams] of int16; d_outs[k] is bank k's output
+ * block of out_type, same pitch in elements.  The banks need not share a history, a filter order, a derivative or a time_step.
+ * CONTRACT.  Let bank k's twin be a bank of the same configuration, flags and history that takes the single savgol_streambank_push_block_i16(twin,
+ * d_samples, ticks, d_outs[k], out_type, stream).  Output k equals the twin's output byte for byte (fp32 outputs: NaN positions coincide, NaN payloads
+ * are free); rows of ticks without an output are not written; bank k's counters, write position and ring are the twin's (the savgol_streambank_save
+ * blobs are byte-equal); produced[k] is the twin's return value (`produced` may be NULL).  By the single call's own contract every output is therefore
+ * also savgol_streambank_push_block_multi's output on the samples widened exactly to fp32; int16 outputs are that output converted ONCE: rounded to
+ * nearest, ties to even; saturated to [-32768, 32767], so +-Inf saturate; NaN gives 0.  No tolerance anywhere.  Returns the smallest produced[k], -1 on
+ * error; ticks == 0 returns 0.
+ * Two routes, chosen before anything is enqueued (csrc/sg_stream_host.hpp, block_plan_multi_i16).  FUSED needs all of: count >= 2; every bank the same
+ * half window n and the same SAVGOL_STREAMBANK_FMA flag; n <= 8 (both bank kinds, two and three outputs per launch); streams % 128 == 0; the samples,
+ * every output and every ring 16-byte aligned; more than 64 ticks; every bank's twin takes its tap-by-tap LDS-DMA tiles.  Then the first 64 ticks are
+ * widened once into fp32 scratch and go, bank after bank, through the bank's own fp32 tiles on its own ring and are converted out (the twin's own
+ * head); the rest of the block goes through one launch that reads each int16 row once and feeds every output (two or three outputs: one launch; four:
+ * two launches of two; csrc/sg_stream_dma_multi_i16.hip); every ring takes its newest samples.  Every other call is `count` single
+ * savgol_streambank_push_block_i16 calls in the caller's order.  A fused call makes launches plus ONE stream-ordered allocation / free pair from the
+ * library's pool, like the single int16 call: capturable after one warm-up call.
+ * Returns -1 with a text naming the call, before any launch or scratch allocation, every bank untouched; checked in this order: NULL banks / d_outs /
+ * d_samples; count outside 1..4; a NULL banks[k] or d_outs[k]; an out_type other than SAVGOL_HIP_I16 / SAVGOL_HIP_F32 (named); a bank listed twice; a
+ * bank with another `streams` than banks[0]; a bank on another device or with the tick service running; more than 2^30 ticks; d_outs[k] sharing a
+ * byte with the samples or with an earlier d_outs[j] (compared byte-wise, each buffer with its own element size).
+ * _route enqueues nothing and changes nothing: -1 on the refusals above, else the number of fused launches the call would make (0: the call is
+ * `count` single int16 block pushes).
+ * Not served here: what savgol_streambank_push_block_i16 does not serve (uint16 samples, a gain or offset, int16 -> fp16 / bf16 outputs). */
+int    savgol_streambank_push_block_multi_i16(SavgolStreamBank *const *banks, int count, const int16_t *d_samples, size_t ticks,
+                                              void *const *d_outs, int out_type, int *produced, void *stream);
+int    savgol_streambank_push_block_multi_i16_route(SavgolStreamBank *const *banks, int count, const int16_t *d_samples, size_t ticks,
                                                     void *const *d_outs, int out_type);
 /* trailing / leading edge rows, up to n of them; -1 on bad arguments, 0 if never filled       */
 int    savgol_streambank_flush(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream);

@@ -159,6 +159,8 @@ SIGNATURES = {
     "savgol_streambank_push_block_multi_route": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp]),
     "savgol_streambank_push_block_multi_h16": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _sz, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
     "savgol_streambank_push_block_multi_h16_route": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _sz, _vp, C.c_int]),
+    "savgol_streambank_push_block_multi_i16": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
+    "savgol_streambank_push_block_multi_i16_route": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, C.c_int]),
     "savgol_streambank_flush": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_flush_leading": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "savgol_streambank_ready": (C.c_bool, [_vp]),
@@ -631,6 +633,32 @@ def push_block_multi_h16_route(banks, samples, dtype, ticks, outs, out_dtype=Non
     b, o = _multi_args(banks, outs)
     it, ot = _multi_h16_types(dtype, out_dtype)
     return lib().savgol_streambank_push_block_multi_h16_route(b, len(banks), _addr(samples), it, ticks, o, ot)
+
+
+def _multi_i16_type(out_dtype):
+    types = {"i16": SAVGOL_HIP_I16, "f32": SAVGOL_HIP_F32}
+    if out_dtype not in types:
+        raise ValueError(f"push_block_multi_i16: out_dtype {out_dtype!r} (\"i16\" or \"f32\")")
+    return types[out_dtype]
+
+
+def push_block_multi_i16(banks, samples, ticks, outs, out_dtype="i16", stream=None):
+    """savgol_streambank_push_block_multi_i16: up to four StreamBanks take the same block of int16 samples, read from memory once; outs[k] is bank k's
+    output block of out_dtype ("i16" or "f32").  Returns the list of produced counts, one per bank (each the single savgol_streambank_push_block_i16's
+    return value); raises on a refusal."""
+    b, o = _multi_args(banks, outs)
+    ot = _multi_i16_type(out_dtype)
+    produced = (C.c_int * max(len(banks), 1))()
+    if lib().savgol_streambank_push_block_multi_i16(b, len(banks), _addr(samples), ticks, o, ot, produced, _stream(stream)) < 0:
+        raise RuntimeError(last_error())
+    return list(produced)[:len(banks)]
+
+
+def push_block_multi_i16_route(banks, samples, ticks, outs, out_dtype="i16"):
+    """the number of fused launches push_block_multi_i16 would make on these arguments (0 = one single int16 block push per bank), -1 on a refusal;
+    enqueues nothing"""
+    b, o = _multi_args(banks, outs)
+    return lib().savgol_streambank_push_block_multi_i16_route(b, len(banks), _addr(samples), ticks, o, _multi_i16_type(out_dtype))
 
 
 class Filter2D:

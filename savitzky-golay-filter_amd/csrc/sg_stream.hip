@@ -37,6 +37,7 @@
 #include "sg_stream_i16.hpp"
 #include "sg_stream_multi.hpp"
 #include "sg_stream_multi_h16.hpp"
+#include "sg_stream_multi_i16.hpp"
 #include "sg_stream_roll.hpp"
 
 extern "C" int sg_small_stream_rows(void *ctx, const float *d_table, const float *ring, int ws, int wp, float dt_inv, int count, const int *row,
@@ -824,7 +825,7 @@ int savgol_streambank_push_block(SavgolStreamBank *bank, const float *d_samples,
 // ---- savgol_streambank_push_block_h16 and savgol_streambank_push_block_i16: one route, two storages ----
 namespace {
 const char *h16_type_name(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
-size_t h16_elem(int t) { return t == SAVGOL_HIP_F32 ? 4 : 2; }         // bytes of an element of a served type
+size_t h16_elem(int t) { return t == SAVGOL_HIP_F32 ? 4 : 2; }         // bytes of an element of a served type (f16, bf16 and i16: two)
 // the two switches of block_form (sg_stream_host.hpp), read once, as sg_bank_roll_launch reads them
 bool stream_dma_switch() { static const int v = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }(); return v != 0; }
 bool stream_moment_switch() { static const int v = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }(); return v != 0; }
@@ -1036,7 +1037,7 @@ int savgol_streambank_push_block_i16(SavgolStreamBank *bank, const int16_t *d_sa
 
 }  // extern "C"
 
-// ---- savgol_streambank_push_block_multi and savgol_streambank_push_block_multi_h16: one route, two storages ----
+// ---- savgol_streambank_push_block_multi, savgol_streambank_push_block_multi_h16 and savgol_streambank_push_block_multi_i16: one route, three storages ----
 namespace {
 struct MultiCall {
     sg::MultiBank bank[SAVGOL_STREAM_MULTI_MAX_BANKS];
@@ -1044,8 +1045,9 @@ struct MultiCall {
     sg::MultiPlan plan;
 };
 
-// What the two fused calls differ in, the storage of the samples and of the outputs: the element types, the type-pair check, the texts of the overlap
-// refusals, the plan, the body's job and launchers, the tail store and the single call (SINGLE plans, and the rest of a partly refused call).
+// What the three fused calls differ in, the storage of the samples and of the outputs: the element types, the type-pair check, the texts of the overlap
+// refusals, the plan, the widening and the conversion of a staged head, the body's job and launchers, the tail store and the single call (SINGLE plans,
+// and the rest of a partly refused call).
 struct FusedF32 {
     typedef float Sample;
     typedef float Out;
@@ -1098,6 +1100,8 @@ struct FusedH16 {
     }
     template <class... A> static sg::MultiPlan plan(A &&...a) { return sg::block_plan_multi_h16(static_cast<A &&>(a)...); }
     void types_into(Job *job) const { job->in_type = (unsigned)in_type; job->out_type = (unsigned)out_type; }
+    void widen_head(const Sample *in, float *out, size_t count, hipStream_t st) const { h16_widen(in, out, count, in_type == SAVGOL_HIP_BF16, st); }
+    void round_head(const float *in, Out *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { h16_round(in, out, streams, first_row, rows, out_type, st); }
     int launch(bool fma, int n, int per, const float *const *center, const Job &job, const sg::MultiPlan &plan, hipStream_t st) const
     {
         return (fma ? sg::sg_bank_dma_multi_h16_launch_fma : sg::sg_bank_dma_multi_h16_launch_ref)(n, per, center, job, plan, st);
@@ -1110,6 +1114,46 @@ struct FusedH16 {
     int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, Out *out, void *stream) const
     {
         return savgol_streambank_push_block_h16(b, samples, in_type, ticks, out, out_type, stream);
+    }
+};
+struct FusedI16 {
+    typedef short Sample;
+    typedef void Out;
+    typedef sg::BankJobMultiH16 Job;                         // its samples are 16-bit words either way
+    static constexpr bool staged_head = true;                // as FusedH16: widened into fp32 scratch, converted out
+    static constexpr int  in_type = SAVGOL_HIP_I16;
+    int out_type;
+    bool types_ok(const char *who) const
+    {
+        if (out_type == SAVGOL_HIP_I16 || out_type == SAVGOL_HIP_F32) return true;
+        sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, h16_type_name(out_type), out_type);
+        return false;
+    }
+    void samples_overlap(const char *who, int k, unsigned long long in_bytes, unsigned long long out_bytes) const
+    {
+        sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of an output may not share a byte)",
+                     who, k, in_bytes, out_bytes);
+    }
+    void outputs_overlap(const char *who, int j, int k, unsigned long long out_bytes) const
+    {
+        sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes %llu bytes of its own)", who, j, k, out_bytes);
+    }
+    template <class... A> static sg::MultiPlan plan(A &&...a) { return sg::block_plan_multi_i16(static_cast<A &&>(a)...); }
+    void types_into(Job *job) const { job->in_type = (unsigned)in_type; job->out_type = (unsigned)out_type; }
+    void widen_head(const Sample *in, float *out, size_t count, hipStream_t st) const { i16_widen(in, out, count, st); }
+    void round_head(const float *in, Out *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { i16_round(in, out, streams, first_row, rows, out_type, st); }
+    int launch(bool fma, int n, int per, const float *const *center, const Job &job, const sg::MultiPlan &plan, hipStream_t st) const
+    {
+        return (fma ? sg::sg_bank_dma_multi_i16_launch_fma : sg::sg_bank_dma_multi_i16_launch_ref)(n, per, center, job, plan, st);
+    }
+    void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t done, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(sg::sg_bank_store_tail_i16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
+                           b->filter->window_size, b->wp, done);
+    }
+    int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, Out *out, void *stream) const
+    {
+        return savgol_streambank_push_block_i16(b, samples, ticks, out, out_type, stream);
     }
 };
 
@@ -1219,7 +1263,7 @@ int fused_push(const S &store, const char *who, SavgolStreamBank *const *banks, 
         if (!scratch) return -1;
         head_in = reinterpret_cast<float *>(scratch);
         head_out = reinterpret_cast<float *>(scratch + frame);
-        h16_widen(d_samples, reinterpret_cast<float *>(scratch), head * streams, store.in_type == SAVGOL_HIP_BF16, st);
+        store.widen_head(d_samples, reinterpret_cast<float *>(scratch), head * streams, st);
     } else {
         head_in = d_samples;
     }
@@ -1236,7 +1280,7 @@ int fused_push(const S &store, const char *who, SavgolStreamBank *const *banks, 
         if constexpr (S::staged_head) {
             const unsigned long long ws = (unsigned long long)b->filter->window_size;
             const size_t silent = b->received + 1 >= ws ? 0 : (size_t)(ws - 1 - b->received);     // head ticks without an output (<= 2n <= 64)
-            h16_round(head_out, d_outs[k], streams, silent, head, store.out_type, st);
+            store.round_head(head_out, d_outs[k], streams, silent, head, st);
         }
     }
     const bool freed = !scratch || sg::scratch_free(scratch, st, who);
@@ -1247,7 +1291,7 @@ int fused_push(const S &store, const char *who, SavgolStreamBank *const *banks, 
         typename S::Job job;
         memset(&job, 0, sizeof(job));
         const float *center[sg::STREAM_MULTI_PER_LAUNCH] = {};
-        job.samples = d_samples; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
+        job.samples = reinterpret_cast<decltype(job.samples)>(d_samples); job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
         store.types_into(&job);
         for (int j = 0; j < per; ++j) {
             const SavgolStreamBank *b = banks[k0 + j];
@@ -1310,6 +1354,17 @@ int savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int c
 {
     return fused_push(FusedH16{in_type, out_type}, "savgol_streambank_push_block_multi_h16", banks, count, static_cast<const unsigned short *>(d_samples), ticks,
                       d_outs, produced, stream);
+}
+
+int savgol_streambank_push_block_multi_i16_route(SavgolStreamBank *const *banks, int count, const int16_t *d_samples, size_t ticks, void *const *d_outs, int out_type)
+{
+    return fused_route(FusedI16{out_type}, "savgol_streambank_push_block_multi_i16_route", banks, count, d_samples, ticks, d_outs);
+}
+
+int savgol_streambank_push_block_multi_i16(SavgolStreamBank *const *banks, int count, const int16_t *d_samples, size_t ticks, void *const *d_outs, int out_type,
+                                           int *produced, void *stream)
+{
+    return fused_push(FusedI16{out_type}, "savgol_streambank_push_block_multi_i16", banks, count, d_samples, ticks, d_outs, produced, stream);
 }
 
 static int bank_edge_rows(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream, bool leading, const char *who)

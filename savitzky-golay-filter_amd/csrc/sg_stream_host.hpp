@@ -1,8 +1,8 @@
 // sg_stream_host.hpp -- host-only rules of the stream block push (no device types: included by g++ translation units too): which form a call takes
 // (block_form), the geometry of its tiles or bands, how taps are packed, the wait counts of the LDS-DMA tiles (DmaQueue) and the routes of the 16-bit
-// call (block_plan_h16), of the fused multi-output call (block_plan_multi) and of the fused multi-output call on 16-bit storage (block_plan_multi_h16).
-// tests/mock/stream_block_forms.cpp, stream_block_h16.cpp, stream_block_multi.cpp, stream_block_multi_h16.cpp, dma_queue.cpp, dma_queue_multi.cpp and
-// dma_queue_multi_h16.cpp print them for tables of call shapes.
+// call (block_plan_h16), of the fused multi-output call (block_plan_multi) and of the fused multi-output call on 16-bit storage (block_plan_multi_h16,
+// block_plan_multi_i16).  tests/mock/stream_block_forms.cpp, stream_block_h16.cpp, stream_block_multi.cpp, stream_block_multi_h16.cpp,
+// stream_block_multi_i16.cpp, dma_queue.cpp, dma_queue_multi.cpp and dma_queue_multi_h16.cpp print them for tables of call shapes.
 #pragma once
 
 #include <cstddef>
@@ -308,6 +308,30 @@ inline MultiPlan block_plan_multi_h16(const MultiBank *banks, int count, size_t 
 {
     return block_plan_fused(banks, count, streams, ticks, misaligned, 0u, dma_switch, moment_switch, static_cast<Fit &&>(moment_terms), stream_multi_h16_max_n,
                             [](int n, bool fma, int outputs) { const MultiH16TileShape s = multi_h16_tile_shape(n, fma, outputs); return MultiTileShape{s.wpb, s.rows / 4}; });
+}
+
+// ---- the fused multi-output block push on int16 storage (savgol_streambank_push_block_multi_i16).  Decided before anything is enqueued ----
+// block_plan_multi_h16's rule word for word (an int16 row is the same 256 bytes per 128 streams; the twin of bank k takes the single
+// savgol_streambank_push_block_i16), with a bound table and a shape table of its own.  A fused call is a head of 64 ticks -- widened once into fp32
+// scratch (i16_widen), then per bank its own fp32 tiles on its own ring and the conversion of their rows (i16_round) --, the body's tiles of all outputs in
+// `launches` launches (sg_stream_dma_multi_i16.hip), then per bank the tail store.
+// SINGLE (launches == 0): everything else -- `count` single savgol_streambank_push_block_i16 calls in the caller's order.
+// Shipped bounds: the h16 table's, 8 for both bank kinds and for 2 and 3 outputs per launch; every tile compiles to the register step of its 16-bit float
+// twin or a better one (tests/test_stream_multi_i16_host.py).  The shipping rule: a (bank kind, outputs, n) stays fused only where the fused call is not
+// behind its single int16 calls by more than the +- 3 % placement spread -- at every fused shape the call's median is 1.09-1.53 x ahead of them on config
+// 3's shape (profiles/stream_multi_i16_time.txt), so nothing was lowered; nothing above 8 has been measured.
+constexpr int stream_multi_i16_max_n(bool fma, int outputs) { return (outputs == 2 || outputs == 3) ? (fma ? 8 : 8) : 0; }   // (fused bank : bit-exact bank)
+// (waves per block, ring ROWS) of a launch: multi_h16_tile_shape's table, the rows are the same bytes
+constexpr MultiH16TileShape multi_i16_tile_shape(int n, bool fma, int outputs)
+{
+    return fma && n == 6 && outputs == 2 ? MultiH16TileShape{8, 24} : MultiH16TileShape{4, 32};
+}
+template <class Fit>
+inline MultiPlan block_plan_multi_i16(const MultiBank *banks, int count, size_t streams, size_t ticks, unsigned misaligned, bool dma_switch, bool moment_switch,
+                                      Fit &&moment_terms)
+{
+    return block_plan_fused(banks, count, streams, ticks, misaligned, 0u, dma_switch, moment_switch, static_cast<Fit &&>(moment_terms), stream_multi_i16_max_n,
+                            [](int n, bool fma, int outputs) { const MultiH16TileShape s = multi_i16_tile_shape(n, fma, outputs); return MultiTileShape{s.wpb, s.rows / 4}; });
 }
 
 }  // namespace sg
