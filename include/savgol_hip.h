@@ -575,6 +575,11 @@ int    savgol_streambank_load(SavgolStreamBank *bank, const void *host_blob, voi
  * Rectangular windows (half_window_x != half_window_y): methods 0 / 2 run the rolling kernel of the LARGER half window on
  * factors zero-padded to it (same results to fp32 rounding).  Caveat of the padding: a zero tap times a non-finite sample is NaN, so in
  * this method NaN / Inf input spreads over the padded (square) window instead of the rectangular one; method 1 does not.
+ * NaN / Inf.  A non-finite input pixel makes non-finite exactly the outputs whose window, after the border remap, contains it (the reference's dense loop skips
+ * no tap: src/savgol2d.c:374-393), and nothing else; a NaN makes them NaN.  Method 1 has the reference's NaN / +Inf / -Inf at the reference's positions;
+ * the separable methods (0, 2, 3) may give NaN where the reference gives +-Inf (two terms can meet as Inf - Inf).  The one exception is the caveat above:
+ * a rectangular window on methods 0 / 2 spreads a special over the square window of its larger half.  The derivative calls and savgol2d_apply_batch_h16
+ * below keep the same rule (the 16-bit call on the frames widened to fp32).
  * The input and output frame stacks must not share a byte (no 2-D kernel can run in place: every output reads its neighbours'
  * inputs): an overlapping call returns -1 with "overlap" in savgol_hip_last_error(); the derivative calls below alike.        */
 int savgol2d_apply_batch_f32(const Savgol2DFilter *filter,
@@ -589,7 +594,8 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter,
  * CONTRACT.  The twin is savgol2d_apply_batch_f32 with the same filter, boundary and method on the frames widened exactly to fp32, in buffers with
  * 16-byte aligned bases, stride = cols rounded up to a multiple of 4 (input and output alike) and image pitch rows x stride.  Every output pixel
  * equals the twin's pixel bit for bit, rounded ONCE to nearest even into out_type (out_type f32: the twin's pixel itself; NaN positions coincide,
- * NaN payloads are free; overflow into fp16 gives +-Inf).  Pixels the twin does not write are not written: the VALID border, and every byte between
+ * NaN payloads are free; overflow into fp16 gives +-Inf; a non-finite input pixel reaches what it reaches in the twin: savgol2d_apply_batch_f32's NaN / Inf
+ * rule).  Pixels the twin does not write are not written: the VALID border, and every byte between
  * cols and the stride and between frames.  None of this depends on the alignment of the caller's buffers.  (The twin's alignment is part of the
  * contract because the fp32 call's additive form re-seeds its rolling column sums at a tile's first row on its tile form and at multiples of U frame
  * rows on its strip walk, which unaligned fp32 buffers take: the two are not the same bits.)
@@ -633,7 +639,8 @@ int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter,
  * one rolling-window launch where they have as many terms; the Laplacian is one frame of the summed kernel
  * scale_xx*Wxx + scale_yy*Wyy.  Other window
  * shapes: one pass per output as savgol2d_apply_batch_f32 method 0 runs it; the Laplacian computes both dense sums from
- * one read of each input tile and adds them as the reference adds its two frames (bit-identical).  See DESIGN.md.    */
+ * one read of each input tile and adds them as the reference adds its two frames (bit-identical).  See DESIGN.md.
+ * NaN / Inf: the rule of savgol2d_apply_batch_f32, every frame under its own (deriv_x, deriv_y) filter; the Laplacian's xx and yy share one window.    */
 int savgol2d_gradient_batch_f32(int half_win_x, int half_win_y, int poly_order,
                                 const float *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
                                 float *d_grad_x, float *d_grad_y, int out_stride, size_t out_image_pitch,

@@ -85,7 +85,11 @@ __device__ __forceinline__ void hf_item(const Job2D &job, const HfTaps<N, NT> &t
         // size; and the last term takes sum_k q_k not from the rounded taps but from the REFERENCE's dense table (sig, fitted on the host: what this
         // term must sum to for the rows of  sum_t G_t(y) sig_t  to equal the row sums of W) -- the systematic part of the taps' rounding.  Emulated
         // (tools/emulate_2d_passes.py --centre): 1.2-2.4e-7 of the output whatever the offset, where the plain pass (and the reference's own loop) grow with it.
-        const f32x2 cc = f32x2{win[s].x, win[s].x};
+        // A non-finite centre counts as 0 (the 1-D kernels' guard): NaN - NaN and Inf - Inf would put a NaN into every tap of the lane's four outputs, the
+        // columns whose window does not hold the pixel included.  With c = 0 the specials meet the taps as in the plain pass; a finite c is untouched.
+        float c = win[s].x;
+        if (!(c - c == 0.0f)) c = 0.0f;
+        const f32x2 cc = f32x2{c, c};
         f32x2 e[2 * R::NQ + 1];
 #pragma unroll
         for (int q = 0; q < R::NQ; ++q) {

@@ -111,6 +111,14 @@ __device__ __forceinline__ f32x2 roll_mul_xb(const f32x2 s, const f32x2 x)
     return p;
 }
 
+// The additive form's shortcuts (rolling sums, sliding corrections, the x-stationary table's two zero taps) carry a NaN or an Inf to outputs whose window does not
+// hold it.  ONE test per row: the carried column sum, folded to one float, is non-finite exactly where a lane's column window holds a special (three adds,
+// v_cmp_class, the wave's vote); the vertical and the horizontal pass branch on that vote (scalar) to cold paths that redo the work the plain way, and only
+// the lanes whose own value was non-finite take the redone value, so a finite lane's bits never depend on its neighbours and a finite frame never leaves
+// the hot path.  (The vote is taken on frame data only: the LDS pads that a strip's halo lanes read are never written and must not be asked.)
+__device__ __forceinline__ bool roll_nonfinite(float v) { return __builtin_amdgcn_class(v, 0x207); }      // sNaN | qNaN | -Inf | +Inf
+__device__ __forceinline__ unsigned long long roll_wave_vote(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 // One item: a 256-column strip whose first loaded column is xload, output rows yb .. yb+nout-1 of one frame.  VEC: the strip's 256
 // input columns are inside the frame, all its SW output columns are stored and rows are 16-byte aligned (one
 // dwordx4 load and store per lane per row); otherwise four remapped scalar loads and masked scalar stores (the
@@ -235,6 +243,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
     f32x4 win[R::U];
 
     f32x2 vbp[2] = {f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f}};    // BOX: box sum of the previous output row minus its oldest input row
+    unsigned long long rowbad[2] = {0ull, 0ull};             // BOX: the wave's vote on the row in LDS row 0 / 1 -- some lane's column window holds a special
     // vertical pass of the output row whose first input row sits in slot u0 -> LDS row `par` (one row per output and term)
     auto vertical = [&](auto u0c, int par) {
         constexpr int u0 = decltype(u0c)::value;
@@ -253,6 +262,24 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
             }
             vbp[0] = vb0 - lo2(win[u0]);                     // the row the next output row no longer sees
             vbp[1] = vb1 - hi2(win[u0]);
+            {
+                // The sum must not carry a non-finite value past the row that brought it: NaN - NaN and Inf - Inf leave a NaN behind when that row leaves,
+                // and it would run down the column until the next re-seed.  A lane whose carried sum is not finite (a special is, or just was, in its
+                // window; or a finite overflow, which only re-seeds) takes the plain sum of the next window's first 2N rows from the ring instead --
+                // in place, under the lane mask: the cold path holds no register of its own.
+                const float carried = (vbp[0].x + vbp[0].y) + (vbp[1].x + vbp[1].y);
+                // The vote is the row's ONE test: vbp is non-finite exactly where vb is (the row that left was in vb's window), and where no lane's vb is,
+                // neither of the two LDS rows this wave writes for the row holds a special -- the horizontal pass asks rowbad, a scalar, and tests nothing.
+                // Every lane votes, the strip's halo lanes too: they hold real frame columns that their neighbours' windows read.
+                rowbad[par] = roll_wave_vote(roll_nonfinite(carried));
+                if (__builtin_expect(rowbad[par] != 0, 0)) {
+                    if (roll_nonfinite(carried)) {
+                        vbp[0] = lo2(win[(u0 + 1) % R::U]); vbp[1] = hi2(win[(u0 + 1) % R::U]);
+#pragma unroll
+                        for (int k = 2; k <= 2 * N; ++k) { vbp[0] = vbp[0] + lo2(win[(u0 + k) % R::U]); vbp[1] = vbp[1] + hi2(win[(u0 + k) % R::U]); }
+                    }
+                }
+            }
             const f32x4 vb = f32x4{vb0.x, vb0.y, vb1.x, vb1.y};
             // term 1, B(y) with B(0) = 0: N folds and N multiply-adds per column pair
             f32x2 v1[2], f[2][N];
@@ -333,7 +360,9 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
         for (int q = 0; q < R::NQ; ++q) hq[u & (NB - 1)][q] = *reinterpret_cast<const f32x4 *>(rd + ((par * NOUT + o) * NT + t) * R::BUFW + 4 * q);
     };
     // one unit's arithmetic on its fetched window, accumulated into r (the first term of an output starts it)
-    auto hterm = [&](auto uc, f32x2 (&r)[2]) {
+    // (par: the LDS row the window came from.  The cold path reads single floats of it again instead of keeping the window registers alive past their last
+    //  use: at a tile's first rows, with the whole ring loaded, there is no register to spare -- the row is not written again before the next step's sync)
+    auto hterm = [&](auto uc, f32x2 (&r)[2], int par) {
         constexpr int u = decltype(uc)::value, o = u / NT, t = u % NT;
         f32x2 e[2 * R::NQ + 1];
 #pragma unroll
@@ -358,6 +387,29 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
             const float s3 = s2 + (wf(hi + 3) - wf(lo + 2));
             r[0] = r[0] + f32x2{s0, s1};
             r[1] = r[1] + f32x2{s2, s3};
+            // Both horizontal units have a shortcut that spreads a special: the sliding correction subtracts what it added, so a non-finite float that has
+            // left an output's window stays in its sum; the x-stationary table's zero taps (a[-1], a[2N+1]) meet the float next to an output's window, and
+            // 0 x NaN = NaN.  Either needs a special in one of the row's two LDS rows, which is what the vertical pass's vote says.  Then a result that is not
+            // finite is summed again over its own window, both units from the floats their LDS rows still hold: a[k] = qx[k].x times float D + j + k of
+            // term 0's row, plus the plain sum of floats lo + j .. hi + j of term 1's.
+            if (__builtin_expect(rowbad[par] != 0, 0)) {
+                const float *const w0 = rd + ((par * NOUT + o) * NT + 0) * R::BUFW, *const w1 = rd + ((par * NOUT + o) * NT + 1) * R::BUFW;
+                auto direct = [&](float &rj, int j) {                // summed in place under the lane mask: the cold path holds no register of its own
+                    if (roll_nonfinite(rj)) {
+                        rj = taps.qx[0].x * w0[R::D + j];
+#pragma unroll
+                        for (int k = 1; k <= 2 * N; ++k) rj = __builtin_fmaf(taps.qx[k].x, w0[R::D + j + k], rj);
+                        float sj = w1[lo + j];
+#pragma unroll
+                        for (int i = lo + j + 1; i <= hi + j; ++i) sj += w1[i];
+                        rj += sj;
+                    }
+                };
+                float r0 = r[0].x, r1 = r[0].y, r2 = r[1].x, r3 = r[1].y;
+                direct(r0, 0); direct(r1, 1); direct(r2, 2); direct(r3, 3);
+                r[0] = f32x2{r0, r1}; r[1] = f32x2{r2, r3};
+                wave_lds_sync();                             // these reads too are ordered before the next write into this LDS row (the next item's first row included)
+            }
             return;
         }
         if constexpr (BOX && NOUT == 1 && t == 0 && TR > 0) {     // tiles only: on the strip walk (n >= 11) the 2N + 2 SGPR pairs cost more than the moves (4-9 % slower)
@@ -497,7 +549,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
             // keep the reads ahead of this unit's arithmetic and that arithmetic ahead of the next unit's: left alone, the
             // scheduler pulls the first consumers of a read (the pair shuffles) up to right behind it and waits there
             __builtin_amdgcn_sched_barrier(0);
-            hterm(uc, r);
+            hterm(uc, r, par);
             if constexpr (ACC && u == UNITS - 1) { r[0] = r[0] + f32x2{prev.x, prev.y}; r[1] = r[1] + f32x2{prev.z, prev.w}; }
             if constexpr (u % NT == NT - 1) store_row(std::integral_constant<int, u / NT>{}, r, yo);
             __builtin_amdgcn_sched_barrier(0);

@@ -198,7 +198,10 @@ __global__ __launch_bounds__(256) void sg2d_separable_kernel(const Job2D job, co
                     // derivative kernels (plan.centre): the taps meet centred samples, s - c with c = the sample in the middle of the segment's 16 + 2N
                     // inputs, and c times what the factor sums to in the reference's dense table is added back -- an offset, a ramp or a slow swing
                     // under the signal then never meets the cancelling taps (and their fp32 rounding) at full size (sg_2d_hf.hip, EXPERIMENTS R6.8)
-                    const float c = plan.centre ? src[N + 8] : 0.0f;
+                    // (a non-finite centre counts as 0, the 1-D kernels' guard: it would reach all 16 outputs of the segment, and for n < 8 the first 8 - n
+                    //  and last 7 - n of them do not have the pixel in their window)
+                    float c = plan.centre ? src[N + 8] : 0.0f;
+                    if (!(c - c == 0.0f)) c = 0.0f;
                     WinConv<N, 16>::template quads<0>([&](int q) { const float4 v = *reinterpret_cast<const float4 *>(src + 4 * q);
                                                                     return make_float4(v.x - c, v.y - c, v.z - c, v.w - c); }, A, Wq, f32x2{0.0f, 0.0f});
                     if (plan.centre) {
