@@ -161,7 +161,15 @@ long savgol_export_header(const SavgolFilter *filter, const char *prefix, const 
  * f64: the same fp32 tables promoted exactly to double, double accumulation, the reference's
  *      float 1/dt_scale promoted -- there is no fp64 path in the reference.
  *      The centre taps must be (anti)symmetric bit for bit, as savgol_create builds them
- *      (tap[k] == +-tap[2n-k]); a hand-edited table that is not returns -1.                   */
+ *      (tap[k] == +-tap[2n-k]); a hand-edited table that is not returns -1.
+ * NaN / Inf.  A non-finite input sample makes non-finite exactly the outputs whose window, after the boundary remap, contains it (the reference's loops skip
+ * no tap: src/savgolFilter.c:547-580, :763-800; a POLYNOMIAL edge row uses all 2n+1 samples of its end, so a special among them reaches all n outputs of that
+ * end), and nothing else; a NaN makes them NaN.  The kernels that apply the taps one by one -- fp32 below half_window 20, second derivatives and poly_order < 2,
+ * PLAIN_SUMMATION, the default fp64 calls, the multi-output and the strided calls -- have the fp64 oracle's NaN / +Inf / -Inf at its positions;
+ * REFERENCE_SUMMATION has the reference's, bit for bit.  The block-moment kernels (fp32 from half_window 20 by default, fp64 under rel_tol >= 1e-6 /
+ * SAVGOL_BATCH_MOMENT_F64 at 24..32, the 16-bit and int16 calls on the same half windows) may give NaN where the reference gives +-Inf: an Inf inside the
+ * samples common to a group's windows makes every moment of that block +-Inf, and their sum mixes signs (Inf - Inf).  In place, VALID and every layout keep
+ * the same rule (tests/test_gpu_1d_nonfinite.py).                                                                                                         */
 int savgol_apply_batch_f32(const SavgolFilter *filter, const float *d_in, float *d_out,
                            size_t channels, size_t length, size_t in_ld, size_t out_ld,
                            void *stream);

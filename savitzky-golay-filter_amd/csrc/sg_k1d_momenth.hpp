@@ -74,6 +74,25 @@ __device__ __forceinline__ void pk_fma_cb(f32x2 &acc, const f32x2 c, const f32x2
     asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "s"(c), "v"(x));
 }
 
+// The two tap pairs with a ZERO partner.  Pair 0 = (w[0], 0) and pair 2n+1 = (0, w[2n]) each feed one output of a pair with a sample that lies one
+// sample outside the other output's window; broadcast like the rest, the zero would meet that sample, and 0 x NaN or 0 x Inf is NaN: one output too many
+// per special sample, on the side its position's parity picks (tests/test_gpu_1d_nonfinite.py).  The zero is multiplied by the sample's neighbour in its
+// register pair instead where that neighbour lies INSIDE the other output's window (the same instruction without the broadcast: a special there belongs to
+// that output anyway), and left out where it does not (a plain single-lane multiply or multiply-add on the half that has a tap).  Finite samples: the
+// same bits either way -- the zero product only ever decides the sign of a sum whose every other term is an exact zero.
+template <int HALF>
+__device__ __forceinline__ f32x2 zero_partner_first(const f32x2 s, const f32x2 x)          // chain 0 of outputs (2j, 2j+1) opens: sample i = x.HALF is tap 0 of output 2j
+{
+    if constexpr (HALF == 0) return pk_mul_ss(s, x);                                         // x.hi = sample i + 1, tap 0 of output 2j + 1
+    else return f32x2{s.x * x.y, 0.0f};
+}
+template <int HALF>
+__device__ __forceinline__ void zero_partner_last(f32x2 &acc, const f32x2 s, const f32x2 x) // sample i = x.HALF is tap 2n of output 2j + 1, one past output 2j's window
+{
+    if constexpr (HALF == 1) pk_fma_ss(acc, s, x);                                           // x.lo = sample i - 1, tap 2n of output 2j
+    else acc.y = __builtin_fmaf(s.y, x.x, acc.y);
+}
+
 template <int N, int M1>
 struct MomentHConv {
     typedef K1D<float, N, 8> K;                              // 8 vectors per lane whatever the plain kernel of this half window uses
@@ -123,7 +142,8 @@ struct MomentHConv {
                     if constexpr (i >= OFF && i < LO) {
                         static_for<8>([&](auto jc) -> bool {
                             constexpr int j = decltype(jc)::value, k = i - OFF - 2 * j;
-                            if constexpr (k >= 0 && k < CH) A[k][j] = pk_mul_xb<(e & 1)>(W[k], e < 2 ? x01 : x23);
+                            if constexpr (k == 0) A[0][j] = zero_partner_first<(e & 1)>(W[0], e < 2 ? x01 : x23);
+                            else if constexpr (k > 0 && k < CH) A[k][j] = pk_mul_xb<(e & 1)>(W[k], e < 2 ? x01 : x23);
                             else if constexpr (k >= CH && k <= HEAD_K1) pk_fma_xb<(e & 1)>(A[k % CH][j], W[k], e < 2 ? x01 : x23);
                             return true;
                         });
@@ -146,7 +166,8 @@ struct MomentHConv {
                     if constexpr (i >= HI && i <= LAST) {
                         static_for<8>([&](auto jc) -> bool {
                             constexpr int j = decltype(jc)::value, k = i - OFF - 2 * j;
-                            if constexpr (k >= TAIL_K0 && k <= 2 * N + 1) pk_fma_xb<(e & 1)>(A[k % CH][j], W[k - TAIL_K0], e < 2 ? x01 : x23);
+                            if constexpr (k == 2 * N + 1) zero_partner_last<(e & 1)>(A[k % CH][j], W[k - TAIL_K0], e < 2 ? x01 : x23);
+                            else if constexpr (k >= TAIL_K0 && k <= 2 * N) pk_fma_xb<(e & 1)>(A[k % CH][j], W[k - TAIL_K0], e < 2 ? x01 : x23);
                             return true;
                         });
                     }

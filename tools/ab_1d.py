@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B two builds of libsavgol_hip.so on the 1-D batch kernel in ONE process, interleaved rounds (rule 24 of the
-CDNA guide: never rank builds across processes/devices).   python tools/ab_1d.py libA.so libB.so [--n 32]"""
+CDNA guide: never rank builds across processes/devices).   python tools/ab_1d.py libA.so libB.so [--n 32] [--storage bf16|i16]
+(--storage: the 16-bit calls, rows of that type in and out: savgol_apply_batch_h16 / savgol_apply_batch_i16)"""
 import argparse
 import ctypes as C
 import sys
@@ -18,6 +19,7 @@ ap.add_argument("--rounds", type=int, default=12)
 ap.add_argument("--f64", action="store_true", help="savgol_apply_batch_f64 on float64 data")
 ap.add_argument("--deriv", type=int, default=0)
 ap.add_argument("--zeros", action="store_true", help="all-zero input (data-dependent power)")
+ap.add_argument("--storage", choices=["f32", "bf16", "i16"], default="f32", help="sample storage of the rows, in and out (fp32 arithmetic inside)")
 a = ap.parse_args()
 
 
@@ -26,6 +28,10 @@ class Cfg(C.Structure):
 
 
 x = (torch.zeros if a.zeros else torch.randn)((a.channels, a.length), dtype=torch.float64 if a.f64 else torch.float32, device="cuda")
+if a.storage == "bf16":
+    x = x.to(torch.bfloat16)
+elif a.storage == "i16":
+    x = (x * 1000.0).round().to(torch.int16)
 y = torch.empty_like(x)
 st = torch.cuda.current_stream().cuda_stream
 libs = []
@@ -50,6 +56,14 @@ for spec in a.libs:
     cfg = Cfg(a.n, a.m, a.deriv, 1.0, 1)
     f = L.savgol_create(C.byref(cfg))
     run = lambda fn=fn, f=f: fn(f, x.data_ptr(), y.data_ptr(), a.channels, a.length, a.length, a.length, st)
+    if a.storage == "bf16":                                  # SAVGOL_HIP_BF16 = 2 in and out, flags 0
+        fn = L.savgol_apply_batch_h16
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_size_t] * 4 + [C.c_uint, C.c_void_p]
+        run = lambda fn=fn, f=f: fn(f, x.data_ptr(), 2, y.data_ptr(), 2, a.channels, a.length, a.length, a.length, 0, st)
+    elif a.storage == "i16":                                 # SAVGOL_HIP_I16 = 3 out, flags 0
+        fn = L.savgol_apply_batch_i16
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_size_t] * 4 + [C.c_uint, C.c_void_p]
+        run = lambda fn=fn, f=f: fn(f, x.data_ptr(), y.data_ptr(), 3, a.channels, a.length, a.length, a.length, 0, st)
     assert run() == 0
     for k, v in saved.items():
         if v is None: os.environ.pop(k, None)
@@ -63,4 +77,4 @@ for r in range(a.rounds):
         ts.append(e0.elapsed_time(e1))
 for path, run, ts in libs:
     ts = np.sort(np.array(ts))
-    print(f"{path:50s} n={a.n}: median {np.median(ts):.3f} ms  min {ts[0]:.3f}  max {ts[-1]:.3f}")
+    print(f"{path:50s} {a.storage} n={a.n}: median {np.median(ts):.3f} ms  min {ts[0]:.3f}  max {ts[-1]:.3f}")
