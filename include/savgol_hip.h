@@ -323,9 +323,9 @@ int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, i
  *   4. input and output rows that share a byte (compared byte-wise: the element sizes may differ; in place is not served).
  * channels == 0 returns 0.  Rows whose base and pitch keep every group of four elements naturally aligned (8 bytes for int16 rows, 16 for fp32
  * output) move as vectors; any other base or pitch is served element by element.  Like its siblings it only enqueues (after one warm-up call with
- * the same filter), so it can be captured into a graph.  Not served on int16: uint16 samples, a gain or offset per call or channel,
- * int16 -> fp16 / bf16 outputs, the multi-output, strided and 2-D calls, in place.  The stream bank's block push on int16:
- * savgol_streambank_push_block_i16 below. */
+ * the same filter), so it can be captured into a graph.  Several filters on one read of int16 rows: savgol_apply[_valid]_multi_batch_i16 below.
+ * Not served on int16: uint16 samples, a gain or offset per call or channel, int16 -> fp16 / bf16 outputs, the strided and 2-D calls, in place.
+ * The stream bank's block push on int16: savgol_streambank_push_block_i16 below. */
 enum { SAVGOL_HIP_I16 = 3 };   /* joins SAVGOL_HIP_F32 / _F16 / _BF16 */
 int savgol_apply_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type,
                            size_t channels, size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream);
@@ -363,6 +363,41 @@ int savgol_apply_multi_batch_h16(const SavgolFilter *const *filters, int count,
 /* the same with savgol_apply_valid's outputs: length - 2n elements at d_outs[k][c*out_ld + 0..] */
 int savgol_apply_valid_multi_batch_h16(const SavgolFilter *const *filters, int count,
                                        const void *d_in, int in_type, void *const *d_outs, int out_type,
+                                       size_t channels, size_t length, size_t in_ld, size_t out_ld,
+                                       unsigned flags, void *stream);
+
+/* Several filters on ONE batch of int16 rows in one pass: the multi-output call on int16 storage.  2 + 2 count bytes per input sample
+ * (int16 -> int16) instead of count x 4 for count single calls; 8 bytes for a smoothed trace and two derivatives.
+ * `filters` and `d_outs` are host arrays of `count` entries, 1 <= count <= SAVGOL_MULTI_MAX_FILTERS, as in savgol_apply_multi_batch_f32; all filters
+ * share config.half_window and config.boundary.  d_in holds rows of int16 elements; EVERY output holds rows of `out_type` elements, SAVGOL_HIP_I16
+ * or SAVGOL_HIP_F32, with the one pitch out_ld; in_ld and out_ld count elements of their own buffer.
+ * CONTRACT: output k equals, bit for bit,
+ *   savgol_apply[_valid]_batch_i16(filters[k], d_in, d_outs[k], out_type, ..., flags | SAVGOL_BATCH_PLAIN_SUMMATION, stream)
+ * and, equivalently, output k of savgol_apply[_valid]_multi_batch_f32(filters, widen(d_in), ..., flags | SAVGOL_BATCH_TILE_NARROW), where widen is
+ * the exact int16 -> fp32 conversion.  For out_type F32 it is that output itself (NaN positions coincide; NaN payloads are free).  For out_type I16
+ * each fp32 result is converted ONCE, just before it is stored: rounded to nearest, ties to even; saturated to [-32768, 32767], so +-Inf saturate;
+ * NaN gives 0.
+ * `flags` is a complete SAVGOL_BATCH_* word: SAVGOL_BATCH_PLAIN_SUMMATION (implied), SAVGOL_BATCH_TILE_NARROW (implied) and
+ * SAVGOL_BATCH_CORRECT_LEADING_EDGE are served.  The narrow tile is implied, so the fp32 call's wide-tile exception does not exist here: every
+ * output fuses.  2 or 3 outputs are one launch, 4 are two launches of two (the input is read twice), 1 is the single int16 call with
+ * SAVGOL_BATCH_PLAIN_SUMMATION.  Outputs land in the caller's order.
+ * Returns -1 with a text naming the call, before any device call; the checks run in this order and the first fault wins:
+ *   1. flags: SAVGOL_BATCH_REFERENCE_SUMMATION, then SAVGOL_BATCH_TILE_WIDE, then flags of other calls (BOUNDARY_AWARE, MOMENT_F64), then unknown bits;
+ *   2. an out_type other than SAVGOL_HIP_I16 / SAVGOL_HIP_F32;
+ *   3. a NULL `filters`, `d_outs` or `d_in`;   4. count outside 1..4;   5. a NULL or malformed filters[k] / a NULL d_outs[k], k ascending;
+ *   6. filters[k] with another half_window, then another boundary, than filters[0], k ascending;
+ *   7. length < window, then channels longer than 2^30 samples, then a pitch smaller than the row;
+ *   8. for k ascending: d_outs[k] sharing a byte with the input rows, then with the rows of d_outs[j], j < k (compared byte-wise: the element
+ *      sizes may differ; in place is not served).
+ * channels == 0 returns 0.  Like its siblings it only enqueues (after one warm-up call with the same filters), so it can be captured into a graph.
+ * Not served: uint16 samples, int16 -> fp16 / bf16 outputs, a gain or offset per channel, in place. */
+int savgol_apply_multi_batch_i16(const SavgolFilter *const *filters, int count,
+                                 const int16_t *d_in, void *const *d_outs, int out_type,
+                                 size_t channels, size_t length, size_t in_ld, size_t out_ld,
+                                 unsigned flags, void *stream);
+/* the same with savgol_apply_valid's outputs: length - 2n elements at d_outs[k][c*out_ld + 0..] */
+int savgol_apply_valid_multi_batch_i16(const SavgolFilter *const *filters, int count,
+                                       const int16_t *d_in, void *const *d_outs, int out_type,
                                        size_t channels, size_t length, size_t in_ld, size_t out_ld,
                                        unsigned flags, void *stream);
 

@@ -142,6 +142,8 @@ SIGNATURES = {
     "savgol_apply_valid_batch_i16": (C.c_int, [_F, _vp, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_multi_batch_h16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.c_int, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_multi_batch_h16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.c_int, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_multi_batch_i16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
+    "savgol_apply_valid_multi_batch_i16": (C.c_int, [C.POINTER(_F), C.c_int, _vp, C.POINTER(_vp), C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_apply_valid_batch_h16": (C.c_int, [_F, _vp, C.c_int, _vp, C.c_int, _sz, _sz, _sz, _sz, C.c_uint, _vp]),
     "savgol_hip_default_flags": (C.c_uint, []),
     # savgol_hip.h: stream bank
@@ -411,6 +413,26 @@ def apply_multi_batch(filters, d_in, d_outs, channels, length, in_ld=None, out_l
         raise RuntimeError(f"{name} returned {rc}: {last_error()}")
 
 
+def apply_multi_batch_i16(filters, d_in, d_outs, channels, length, in_ld=None, out_ld=None, out_dtype="i16", flags=0, valid=False, stream=None):
+    """savgol_apply[_valid]_multi_batch_i16: several Filters of one half window and boundary on one read of d_in (int16 device memory), every output of
+    out_dtype "i16" or "f32".  in_ld / out_ld count elements of their own buffer; d_outs[k] is bit-identical to filters[k].apply_batch_i16(...,
+    out_dtype=out_dtype, flags=flags | SAVGOL_BATCH_PLAIN_SUMMATION)."""
+    types = {"i16": SAVGOL_HIP_I16, "f32": SAVGOL_HIP_F32}
+    if out_dtype not in types:
+        raise ValueError(f"apply_multi_batch_i16: out_dtype {out_dtype!r} (\"i16\" or \"f32\")")
+    count = len(filters)
+    if len(d_outs) != count:
+        raise ValueError("one output per filter")
+    n = filters[0].n if count else 0
+    fs = (_F * max(count, 1))(*[f.ptr for f in filters])
+    outs = (_vp * max(count, 1))(*[_addr(o) for o in d_outs])
+    name = f"savgol_apply_{'valid_' if valid else ''}multi_batch_i16"
+    rc = getattr(lib(), name)(fs, count, _addr(d_in), outs, types[out_dtype], channels, length, length if in_ld is None else in_ld,
+                              (length - 2 * n if valid else length) if out_ld is None else out_ld, flags, _stream(stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} returned {rc}: {last_error()}")
+
+
 def _field_jobs(jobs):
     return (SavgolFieldJob * max(len(jobs), 1))(*[SavgolFieldJob(f.ptr, in_offset, out_offset) for f, in_offset, out_offset in jobs])
 
@@ -447,6 +469,23 @@ def apply_multi_tensor(filters, x, valid=False, flags=0, stream=None, out_dtype=
     ys = [torch.empty((ch, out_len), dtype=x.dtype if out_dtype is None else out_dtype, device=x.device) for _ in filters]
     apply_multi_batch(filters, x, ys, ch, length, length, out_len, flags=flags, valid=valid, stream=stream, dtype=dtype,
                       out_dtype=None if out_dtype is None else names[out_dtype])
+    return ys
+
+
+def apply_multi_tensor_i16(filters, x, valid=False, flags=0, out_dtype=None, stream=None):
+    """x: contiguous 2-D torch.int16 tensor [channels, length] on the GPU; returns one tensor per filter (same order).  out_dtype: None = int16, or
+    torch.float32."""
+    import torch
+    if x.dtype != torch.int16:
+        raise TypeError(f"apply_multi_tensor_i16 serves int16 tensors, not {x.dtype}")
+    if out_dtype not in (None, torch.int16, torch.float32):
+        raise TypeError(f"apply_multi_tensor_i16: {x.dtype} -> {out_dtype} is not served")
+    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
+    ch, length = x.shape
+    out_len = length - 2 * filters[0].n if valid else length
+    ys = [torch.empty((ch, out_len), dtype=torch.int16 if out_dtype is None else out_dtype, device=x.device) for _ in filters]
+    apply_multi_batch_i16(filters, x, ys, ch, length, length, out_len, out_dtype="f32" if out_dtype == torch.float32 else "i16", flags=flags, valid=valid,
+                          stream=stream)
     return ys
 
 

@@ -18,6 +18,7 @@
 #include "sg_k1d_h16_host.hpp"
 #include "sg_k1d_i16_host.hpp"
 #include "sg_k1d_multi_h16_host.hpp"
+#include "sg_k1d_multi_i16_host.hpp"
 #include "sg_k1d_strided_multi_launch.hpp"
 #include "sg_runtime.hpp"
 
@@ -813,23 +814,30 @@ const char *i16_storage_name(int t)
 
 constexpr const char *I16_TOO_LONG = "%s: channels longer than 2^30 samples (%zu) are not served on int16 storage";
 
-int enqueue_i16(const char *who, const SavgolFilter *f, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
-                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+// what both int16 routes refuse first, in this order: the flags they do not serve, then the output type
+bool i16_call_served(const char *who, unsigned flags, int out_type)
 {
     if (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) {
         sg_set_error("%s: SAVGOL_BATCH_REFERENCE_SUMMATION is not served on int16 storage (the reference has no int16 form to be identical to)", who);
-        return -1;
+        return false;
     }
-    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on int16 storage (the call runs the narrow tile)", who); return -1; }
+    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on int16 storage (the call runs the narrow tile)", who); return false; }
     if (flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64)) {
         sg_set_error("%s: flags 0x%x belong to other calls (BOUNDARY_AWARE: strided calls, MOMENT_F64: fp64 calls)", who, flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64));
-        return -1;
+        return false;
     }
-    if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return -1; }
+    if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return false; }
     if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
         sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, i16_storage_name(out_type), out_type);
-        return -1;
+        return false;
     }
+    return true;
+}
+
+int enqueue_i16(const char *who, const SavgolFilter *f, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
+                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+{
+    if (!i16_call_served(who, flags, out_type)) return -1;
     if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, I16_TOO_LONG)) return -1;
     if (channels == 0) return 0;
     const int n = f->config.half_window;
@@ -929,6 +937,73 @@ int enqueue_multi_h16(const char *who, const SavgolFilter *const *filters, int c
             j.multi.base.total_tiles = (unsigned)(g.nc * tpc);
             j.multi.base.edge_items = shape.want_edges ? (unsigned)(2 * g.nc * (size_t)K) : 0u;
             if (sg1d_launch_multi_h16(n, K, &j, &taps, grid_blocks(j.multi.base.total_tiles + j.multi.base.edge_items), st) != 0) return -1;
+        }
+        g0 += K;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Several filters on one read of int16 rows (savgol_apply[_valid]_multi_batch_i16): enqueue_multi_h16's route with enqueue_i16's storage rules, on
+// sg1d_multi_i16_kernel (sg_k1d_multi_i16.hpp).  The narrow tile and the plain summation are implied, so every output fuses: 2 or 3 outputs are one
+// launch, 4 are two launches of two, 1 is the int16 single call with SAVGOL_BATCH_PLAIN_SUMMATION.  The checks, in this order (the first fault wins):
+//   1. flags, as enqueue_i16: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the output type;
+//   3. NULL filters / d_outs / d_in;   4. count;   5. a NULL or malformed entry, k ascending;   6. half_window, then boundary, of filters[k] against
+//   filters[0], k ascending;   7. check_rows: length < window, channels beyond 2^30 samples, pitches;   (zero channels: 0, nothing enqueued)
+//   8. shared bytes, k ascending: d_outs[k] against d_in, then against d_outs[j], j < k;   9. the kernel objects are linked;   10. a usable device.
+// ------------------------------------------------------------------------------------------------
+int enqueue_multi_i16(const char *who, const SavgolFilter *const *filters, int count, const int16_t *d_in, void *const *d_outs, int out_type,
+                      size_t channels, size_t length, size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+{
+    if (!i16_call_served(who, flags, out_type)) return -1;
+    if (!filters || !d_outs || !d_in) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (count < 1 || count > SAVGOL_MULTI_MAX_FILTERS) { sg_set_error("%s: count %d outside 1..%d", who, count, SAVGOL_MULTI_MAX_FILTERS); return -1; }
+    if (!multi_filters_match(who, filters, d_outs, count)) return -1;
+    const SavgolFilter *f0 = filters[0];
+    const int n = f0->config.half_window;
+    if (!check_rows(who, f0, d_in, d_outs[0], length, in_ld, out_ld, variant, I16_TOO_LONG)) return -1;
+    if (channels == 0) return 0;
+    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
+    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
+    for (int k = 0; k < count; ++k) {
+        if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_outs[k], out_ld * ob, out_len * ob, channels)) {
+            sg_set_error("%s: d_outs[%d] overlaps d_in (the multi-output call does not run in place: input and output rows may not share a byte)", who, k);
+            return -1;
+        }
+        for (int j = 0; j < k; ++j)
+            if (rows_overlap_bytes((uintptr_t)d_outs[j], out_ld * ob, out_len * ob, (uintptr_t)d_outs[k], out_ld * ob, out_len * ob, channels)) {
+                sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap", who, j, k);
+                return -1;
+            }
+    }
+    if (count == 1) return enqueue_i16(who, f0, d_in, d_outs[0], out_type, channels, length, in_ld, out_ld, variant, st, flags | SAVGOL_BATCH_PLAIN_SUMMATION);
+    if (!sg1d_launch_multi_i16) { sg_set_error("%s: the int16 multi-output kernels are not part of this build (object not linked)", who); return -1; }
+
+    DeviceCtx *ctx = sg::ctx_get();
+    if (!ctx) return -1;
+    const CallShape shape = call_shape(f0, variant, length);
+    constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
+    sg::JobMultiI16 ji;
+    memset(&ji, 0, sizeof(ji));
+    sg::JobMulti1D &jm = ji.multi;
+    job_init(jm.base, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
+    ji.out_type = (unsigned)out_type;
+    const unsigned tpc = jm.base.tiles_per_channel;
+    const int all[SAVGOL_MULTI_MAX_FILTERS] = {0, 1, 2, 3};
+
+    // launches of 3, 2 or 2 + 2 outputs
+    for (int g0 = 0; g0 < count;) {
+        const int K = (count - g0 == 4) ? 2 : (count - g0);
+        sg::TapsMulti taps;
+        if (!multi_launch_outputs(ctx, jm, taps, filters, d_outs, all + g0, K, shape, flags, out_ld, ob)) return -1;
+        // the edge items of every output counted
+        for (ChannelGroups g{channels, launch_max_channels(tpc, 2 * (unsigned)K)}; g.next();) {
+            sg::JobMultiI16 j = ji;
+            j.multi.base.in = reinterpret_cast<const char *>(d_in) + g.c0 * in_ld * ib;
+            for (int o = 0; o < K; ++o) j.multi.out[o] = static_cast<char *>(jm.out[o]) + g.c0 * out_ld * ob;
+            j.multi.base.total_tiles = (unsigned)(g.nc * tpc);
+            j.multi.base.edge_items = shape.want_edges ? (unsigned)(2 * g.nc * (size_t)K) : 0u;
+            if (sg1d_launch_multi_i16(n, K, &j, &taps, grid_blocks(j.multi.base.total_tiles + j.multi.base.edge_items), st) != 0) return -1;
         }
         g0 += K;
     }
@@ -1227,6 +1302,20 @@ int savgol_apply_valid_multi_batch_h16(const SavgolFilter *const *filters, int c
                                        size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
     return enqueue_multi_h16("savgol_apply_valid_multi_batch_h16", filters, count, d_in, in_type, d_outs, out_type, channels, length, in_ld, out_ld, VALID,
+                             static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_multi_batch_i16(const SavgolFilter *const *filters, int count, const int16_t *d_in, void *const *d_outs, int out_type, size_t channels,
+                                 size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_multi_i16("savgol_apply_multi_batch_i16", filters, count, d_in, d_outs, out_type, channels, length, in_ld, out_ld, FULL,
+                             static_cast<hipStream_t>(stream), flags);
+}
+
+int savgol_apply_valid_multi_batch_i16(const SavgolFilter *const *filters, int count, const int16_t *d_in, void *const *d_outs, int out_type, size_t channels,
+                                       size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
+{
+    return enqueue_multi_i16("savgol_apply_valid_multi_batch_i16", filters, count, d_in, d_outs, out_type, channels, length, in_ld, out_ld, VALID,
                              static_cast<hipStream_t>(stream), flags);
 }
 

@@ -1,0 +1,25 @@
+// sg_k1d_multi_i16.hip -- instantiates sg1d_multi_i16_kernel<N, SG_MULTI_K> (sg_k1d_multi_i16.hpp) for N in [SG_NLO, SG_NHI] and exports one launcher
+// for that (output count, half-window group).  Compiled once per pair by the Makefile, with the half-window groups of sg_k1d_inst.hip.
+#include "sg_k1d_multi_i16.hpp"
+
+#if !defined(SG_MULTI_K) || !defined(SG_NLO) || !defined(SG_NHI) || !defined(SG_FN)
+#error "compile with -DSG_MULTI_K=2|3 -DSG_NLO=.. -DSG_NHI=.. -DSG_FN=symbol"
+#endif
+
+namespace sg {
+
+template <int N, int HI>
+static int dispatch_multi_i16(int n, const JobMultiI16 &job, const TapsMulti &taps, unsigned grid, hipStream_t st)
+{
+    if (n == N) { hipLaunchKernelGGL((sg1d_multi_i16_kernel<N, SG_MULTI_K>), dim3(grid), dim3(256), 0, st, job, taps); return 1; }     // `grid` counts blocks of 4 tiles
+    if constexpr (N < HI) return dispatch_multi_i16<N + 1, HI>(n, job, taps, grid, st);
+    else return 0;
+}
+
+}  // namespace sg
+
+// returns 1 if this group owns half window n (kernel enqueued), 0 otherwise
+extern "C" int SG_FN(int n, const sg::JobMultiI16 *job, const sg::TapsMulti *taps, unsigned grid, void *stream)
+{
+    return sg::dispatch_multi_i16<SG_NLO, SG_NHI>(n, *job, *taps, grid, static_cast<hipStream_t>(stream));
+}
