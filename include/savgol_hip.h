@@ -663,7 +663,7 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter,
  * freed in stream order, d_out is untouched): method 2 or 3 on a filter for which the fp32 call has no separable kernel ("no separable kernel ...").
  * images == 0 returns 0.  Like its siblings it only enqueues (after one warm-up call with the same filter), so it can be captured into a graph.
  * Not served in 16 bit: the derivative-frame calls below (a Savgol2DFilter created with deriv_x / deriv_y goes through this call like any other
- * filter), the row-band calls, int16 / uint16 pixels, fp32 -> 16-bit pairs. */
+ * filter), the row-band calls, uint16 pixels (int16 pixels: savgol2d_apply_batch_i16 below; this call keeps refusing SAVGOL_HIP_I16), fp32 -> 16-bit pairs. */
 int savgol2d_apply_batch_h16(const Savgol2DFilter *filter,
                              const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
                              void *d_out, int out_type, int out_stride, size_t out_image_pitch,
@@ -672,6 +672,46 @@ int savgol2d_apply_batch_h16(const Savgol2DFilter *filter,
  * -1 = the call would be refused before any launch (same order, same texts). */
 int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter,
                                    const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
+                                   const void *d_out, int out_type, int out_stride, size_t out_image_pitch,
+                                   size_t images, Savgol2DBoundary boundary, int method);
+
+/* The 2-D batch call on INT16 STORAGE: int16 frames in (detector and camera frames, CT slices, depth and SAR rasters), int16 or fp32 out, fp32
+ * arithmetic inside -- 4 bytes per pixel (int16 -> int16) or 6 (int16 -> fp32) instead of the 12-20 that widening, filtering and converting on the
+ * caller's side keep resident.  out_type: SAVGOL_HIP_I16 or SAVGOL_HIP_F32.  Strides and image pitches count elements of their own buffer's type.
+ * CONTRACT (savgol2d_apply_batch_h16's).  The twin is savgol2d_apply_batch_f32 with the same filter, boundary and method on the frames widened exactly to
+ * fp32, in buffers with 16-byte aligned bases, stride = cols rounded up to a multiple of 4 (input and output alike) and image pitch rows x stride.
+ * An fp32 output pixel is the twin's pixel bit for bit.  An int16 output pixel is the twin's pixel converted ONCE by the rule of the other int16 calls
+ * (csrc/sg_i16.hpp): round to nearest, ties to even; saturate to [-32768, 32767]; NaN -> 0 (stated for uniformity: an int16 frame holds no NaN or Inf,
+ * so a NaN is reachable only through a filter whose scale overflows).  Pixels the twin does not write are not written: the VALID border, and every byte
+ * between cols and the stride and between frames.  None of this depends on the alignment of the caller's buffers.
+ * method: 0, 2 and 3 mean what they mean for the twin.  Method 1 returns -1: the reference has no int16 form to be identical to.
+ * Two routes, chosen by one host rule before anything is enqueued -- the 16-bit call's rule unchanged (csrc/sg_2d_h16_host.hpp, frame_plan_h16: the
+ * element sizes are the same).  TILES -- the twin launches the rolling kernel's additive tile form (a smoothing filter of order <= 3 on a square window,
+ * half windows 1..16; not an x-dominant filter; method 0 or 2), cols % 4 == 0 and cols >= 32, quads are naturally aligned (int16 side: 8-byte base,
+ * stride and pitch multiples of 4; fp32 output: 16-byte base), rows x out_stride x element size and the twin's rows x cols x 4 are under 0x7fffff00,
+ * and neither SAVGOL_HIP_ROLL_TILE nor SAVGOL_HIP_2D_I16_TILES is 0: sg2d_rolling_i16_kernel (csrc/sg_2d_roll_i16.inc), the same tiles reading int16 rows
+ * and storing out_type rows, the storage types fixed when the kernel is compiled.  STAGED -- every other call (the general, two-output,
+ * horizontal-first and accumulating tile forms included) runs the twin itself: whole frames in the 16-bit call's pieces are widened into aligned fp32
+ * scratch (sg2d_i16_widen_kernel), filtered scratch to scratch, and the pixels the twin wrote converted out (sg2d_i16_convert_kernel).  Pieces of whole
+ * frames do not change bits.  SAVGOL_HIP_2D_I16_TILES is read with getenv at every call (SAVGOL_HIP_ROLL_TILE once per process); set it before
+ * threads start.
+ * Returns -1 with a text naming savgol2d_apply_batch_i16, before any launch or scratch allocation; the checks run in this order and the first fault wins:
+ *   1. method 1, or a method outside 0..3;   2. an out_type other than SAVGOL_HIP_I16 / SAVGOL_HIP_F32 (named);   3. a NULL pointer;
+ *   4. an invalid filter struct;   5. the geometry savgol2d_apply_batch_f32 refuses, with its texts;
+ *   6. input and output stacks that share a byte (compared byte-wise: element sizes 2 and 2 or 4; d_in == d_out is an overlap).
+ * The twin's own late refusal is kept as the 16-bit call has it: "no separable kernel ..." on the staged route with method 2 or 3 (d_out untouched).
+ * images == 0 returns 0.  Like its siblings it only enqueues (after one warm-up call with the same filter), so it can be captured into a graph.
+ * Not served: uint16 pixels (12- and 14-bit unsigned data, everything below 32768, can be passed as int16 as it is); a gain or offset per call;
+ * int16 -> fp16 / bf16 pairs; the derivative-frame and row-band calls; in place; the general, two-output, horizontal-first and accumulating tile forms
+ * on int16 rows (they take the staged route); bench.py (the flagship workload stays fp32).  savgol2d_apply_batch_h16 keeps refusing SAVGOL_HIP_I16. */
+int savgol2d_apply_batch_i16(const Savgol2DFilter *filter,
+                             const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
+                             void *d_out, int out_type, int out_stride, size_t out_image_pitch,
+                             size_t images, Savgol2DBoundary boundary, int method, void *stream);
+/* Which route the call above would take for these arguments, decided by the same code and touching no device: 1 = TILES, 0 = STAGED (or no images),
+ * -1 = the call would be refused before any launch (same order, same texts). */
+int savgol2d_apply_batch_i16_route(const Savgol2DFilter *filter,
+                                   const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
                                    const void *d_out, int out_type, int out_stride, size_t out_image_pitch,
                                    size_t images, Savgol2DBoundary boundary, int method);
 

@@ -24,6 +24,7 @@
 
 #include "sg_2d.hpp"
 #include "sg_2d_h16.hpp"
+#include "sg_2d_i16.hpp"
 #include "sg_runtime.hpp"
 
 namespace sg {
@@ -450,6 +451,109 @@ static int host_apply(const char *who, const Savgol2DFilter *f, const float *inp
     return 0;
 }
 
+// ---- what the two 2-D batch calls on 2-byte storage share (savgol2d_apply_batch_h16, savgol2d_apply_batch_i16; the entry points are further down) ----
+static const char *const kH16Who2D = "savgol2d_apply_batch_h16";
+static const char *h16_type_name_2d(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
+static const char *const kI16Who2D = "savgol2d_apply_batch_i16";
+
+// The staged route: the twin itself.  Whole frames per piece, widened into aligned fp32 scratch, savgol2d_apply_batch_f32's own path (enqueue_2d)
+// scratch to scratch, and the pixels it wrote rounded out.  Pieces of whole frames do not change bits: the additive tile's re-seed phase is the
+// tile, the strip walk's the frame row (launch_roll_kernel), and every other 2-D kernel computes its outputs independently.
+// (shared with savgol2d_apply_batch_i16: `widen(first frame, scratch, frames)` and `convert(scratch, first output byte, frames, xlo, xhi, ylo, yhi)` are the
+//  storage family's two small kernels; the element sizes, and with them the pieces, are the same)
+template <class Widen, class Convert>
+static int staged16_2d(const char *who, DeviceCtx *ctx, const Savgol2DFilter *f, int rows, int cols, void *d_out, size_t out_elem, long long out_pitch, size_t images,
+                       int boundary, int method, hipStream_t st, Widen widen, Convert convert)
+{
+    const FrameStageH16 g = frame_stage_h16(rows, cols, images);
+    const size_t side = (g.frames * g.frame * sizeof(float) + 255) & ~(size_t)255;
+    char *scratch = static_cast<char *>(scratch_alloc(ctx, 2 * side, st, who));
+    if (!scratch) return -1;
+    float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + side);
+    const bool valid = boundary == SAVGOL2D_BOUNDARY_VALID;
+    const int nx = f->config.half_window_x, ny = f->config.half_window_y;
+    const int xlo = valid ? nx : 0, xhi = valid ? cols - nx : cols, ylo = valid ? ny : 0, yhi = valid ? rows - ny : rows;
+    int rc = 0;
+    for (size_t i0 = 0; i0 < images && rc == 0; i0 += g.frames) {
+        const size_t ni = images - i0 < g.frames ? images - i0 : g.frames;
+        widen(i0, sin, ni);
+        rc = enqueue_2d(who, f, sin, rows, cols, g.stride, (long long)g.frame, sout, g.stride, (long long)g.frame, ni, boundary, method, st);
+        if (rc != 0) break;
+        convert(sout, static_cast<char *>(d_out) + i0 * (size_t)out_pitch * out_elem, ni, xlo, xhi, ylo, yhi);
+    }
+    const bool freed = scratch_free(scratch, st, who);
+    if (rc != 0 || !freed) return -1;
+    return hip_ok(hipGetLastError(), who) ? 0 : -1;
+}
+
+// The two calls on 2-byte storage (h16, i16) share everything but the check of their types: `form` names the storage in the method text, `tiles_env` is
+// the call's own switch.
+static bool method_ok_16(const char *who, int method, const char *form)
+{
+    if (method == 1) { sg_set_error("%s: method 1 (the dense kernel in the reference's summation order) is not served: the reference has no %s form to be identical to", who, form); return false; }
+    if (method < 0 || method > 3) { sg_set_error("%s: method %d is not one of 0, 2, 3", who, method); return false; }
+    return true;
+}
+// Everything after a call's own type check: the remaining refusals in the header's order, then the route: -1 = refused (text set), 0 = nothing to do
+// (no images) or STAGED, 1 = TILES.  Touches no device.  `factors` / `terms`: the filter's separable factors, for the launch that follows.
+static int plan16_2d(const char *who, const char *tiles_env, const Savgol2DFilter *filter, const void *d_in, int rows, int cols, int in_stride, long long in_pitch,
+                     const void *d_out, int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
+{
+    if (!filter || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
+    if (!filter_ok(who, filter)) return -1;
+    const int nx = filter->config.half_window_x, ny = filter->config.half_window_y;
+    if (!geometry_ok(who, nx, ny, rows, cols, in_stride, out_stride, boundary)) return -1;
+    if (images == 0) return 0;
+    const int out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_in), out0 = reinterpret_cast<uintptr_t>(d_out);
+    if (frames_overlap(in0, 2, in_pitch, in_stride, out0, (size_t)out_elem, out_pitch, out_stride, rows, cols, images)) {
+        sg_set_error("%s: input and output frames overlap (2-D filtering cannot run in place; compared byte-wise)", who);
+        return -1;
+    }
+    // the route (sg_2d_h16_host.hpp).  The call's switch (SAVGOL_HIP_2D_H16_TILES / SAVGOL_HIP_2D_I16_TILES) is read at every call, not once: tools/time_2d_h16.py times both routes interleaved in
+    // one process (single-threaded; the header says so).  SAVGOL_HIP_ROLL_TILE is read once, where the fp32 launcher reads it (roll_tiles_on, inside
+    // the predicate); the rule names it as a condition of its own, so the shape carries it too.
+    const char *const tiles_text = getenv(tiles_env);
+    static const bool roll_tile_env = [] { const char *e = getenv("SAVGOL_HIP_ROLL_TILE"); return !e || atoi(e) != 0; }();
+    *terms = sep_factors_cached(&filter->config, factors);
+    FrameShapeH16 shape;
+    shape.rows = rows; shape.cols = cols;
+    shape.in_stride = in_stride; shape.in_pitch = in_pitch; shape.out_stride = out_stride; shape.out_pitch = out_pitch;
+    shape.in_base = in0; shape.out_base = out0; shape.out_elem = out_elem;
+    shape.method = method;
+    shape.x_dominant = sg2d_x_dominant(filter->config.deriv_x, filter->config.deriv_y);
+    shape.additive_tile = *terms > 0 && sg2d_launch_rolling_h16(nx > ny ? nx : ny, *terms, nullptr, factors, filter->scale, 0, nullptr) == 0;
+    shape.roll_tile_switch = roll_tile_env;
+    shape.tiles_switch = !tiles_text || atoi(tiles_text) != 0;
+    return frame_plan_h16(shape) == FRAME_H16_TILES ? 1 : 0;
+}
+
+static int h16_plan_2d(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, long long in_pitch, const void *d_out,
+                       int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
+{
+    const char *who = kH16Who2D;
+    if (!method_ok_16(who, method, "16-bit")) return -1;
+    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
+        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who, h16_type_name_2d(in_type),
+                     h16_type_name_2d(out_type), in_type, out_type);
+        return -1;
+    }
+    return plan16_2d(who, "SAVGOL_HIP_2D_H16_TILES", filter, d_in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, boundary, method, factors, terms);
+}
+
+// savgol2d_apply_batch_i16: the same, with its own type check (int16 in; int16 or fp32 out)
+static int i16_plan_2d(const Savgol2DFilter *filter, const void *d_in, int rows, int cols, int in_stride, long long in_pitch, const void *d_out, int out_type,
+                       int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
+{
+    const char *who = kI16Who2D;
+    if (!method_ok_16(who, method, "int16")) return -1;
+    if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
+        sg_set_error("%s: out_type %d is not served: SAVGOL_HIP_I16 (%d) and SAVGOL_HIP_F32 (%d) are", who, out_type, SAVGOL_HIP_I16, SAVGOL_HIP_F32);
+        return -1;
+    }
+    return plan16_2d(who, "SAVGOL_HIP_2D_I16_TILES", filter, d_in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, boundary, method, factors, terms);
+}
+
 }  // namespace sg
 
 extern "C" {
@@ -517,35 +621,25 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter, const float *d_in, in
 // ---- the 2-D batch call on 16-bit storage: fp16 / bf16 frames in, the same type or fp32 out, the fp32 call's arithmetic in between ----
 namespace sg {
 
-static const char *const kH16Who2D = "savgol2d_apply_batch_h16";
-static const char *h16_type_name_2d(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
 
-// The staged route: the twin itself.  Whole frames per piece, widened into aligned fp32 scratch, savgol2d_apply_batch_f32's own path (enqueue_2d)
-// scratch to scratch, and the pixels it wrote rounded out.  Pieces of whole frames do not change bits: the additive tile's re-seed phase is the
-// tile, the strip walk's the frame row (launch_roll_kernel), and every other 2-D kernel computes its outputs independently.
 static int h16_staged_2d(DeviceCtx *ctx, const Savgol2DFilter *f, const unsigned short *d_in, bool ibf, int rows, int cols, int in_stride, long long in_pitch,
                          void *d_out, int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, hipStream_t st)
 {
-    const FrameStageH16 g = frame_stage_h16(rows, cols, images);
-    const size_t side = (g.frames * g.frame * sizeof(float) + 255) & ~(size_t)255;
-    char *scratch = static_cast<char *>(scratch_alloc(ctx, 2 * side, st, kH16Who2D));
-    if (!scratch) return -1;
-    float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + side);
-    const bool valid = boundary == SAVGOL2D_BOUNDARY_VALID;
-    const int nx = f->config.half_window_x, ny = f->config.half_window_y;
-    const int xlo = valid ? nx : 0, xhi = valid ? cols - nx : cols, ylo = valid ? ny : 0, yhi = valid ? rows - ny : rows;
-    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
-    int rc = 0;
-    for (size_t i0 = 0; i0 < images && rc == 0; i0 += g.frames) {
-        const size_t ni = images - i0 < g.frames ? images - i0 : g.frames;
-        sg2d_h16_widen_frames(d_in + (long long)i0 * in_pitch, in_stride, in_pitch, ibf, sin, rows, cols, ni, st);
-        rc = enqueue_2d(kH16Who2D, f, sin, rows, cols, g.stride, (long long)g.frame, sout, g.stride, (long long)g.frame, ni, boundary, method, st);
-        if (rc != 0) break;
-        sg2d_h16_round_frames(sout, static_cast<char *>(d_out) + i0 * (size_t)out_pitch * out_elem, out_type, out_stride, out_pitch, rows, cols, xlo, xhi, ylo, yhi, ni, st);
-    }
-    const bool freed = scratch_free(scratch, st, kH16Who2D);
-    if (rc != 0 || !freed) return -1;
-    return hip_ok(hipGetLastError(), kH16Who2D) ? 0 : -1;
+    return staged16_2d(kH16Who2D, ctx, f, rows, cols, d_out, out_type == SAVGOL_HIP_F32 ? 4 : 2, out_pitch, images, boundary, method, st,
+                       [&](size_t i0, float *sin, size_t ni) { sg2d_h16_widen_frames(d_in + (long long)i0 * in_pitch, in_stride, in_pitch, ibf, sin, rows, cols, ni, st); },
+                       [&](const float *sout, void *out, size_t ni, int xlo, int xhi, int ylo, int yhi) {
+                           sg2d_h16_round_frames(sout, out, out_type, out_stride, out_pitch, rows, cols, xlo, xhi, ylo, yhi, ni, st);
+                       });
+}
+
+static int i16_staged_2d(DeviceCtx *ctx, const Savgol2DFilter *f, const short *d_in, int rows, int cols, int in_stride, long long in_pitch, void *d_out, int out_type,
+                         int out_stride, long long out_pitch, size_t images, int boundary, int method, hipStream_t st)
+{
+    return staged16_2d(kI16Who2D, ctx, f, rows, cols, d_out, out_type == SAVGOL_HIP_F32 ? 4 : 2, out_pitch, images, boundary, method, st,
+                       [&](size_t i0, float *sin, size_t ni) { sg2d_i16_widen_frames(d_in + (long long)i0 * in_pitch, in_stride, in_pitch, sin, rows, cols, ni, st); },
+                       [&](const float *sout, void *out, size_t ni, int xlo, int xhi, int ylo, int yhi) {
+                           sg2d_i16_convert_frames(sout, out, out_type, out_stride, out_pitch, rows, cols, xlo, xhi, ylo, yhi, ni, st);
+                       });
 }
 
 }  // namespace sg
@@ -554,46 +648,6 @@ namespace sg {
 
 // The refusals of the 16-bit call in the header's order, then its route: -1 = refused (text set), 0 = nothing to do (no images) or STAGED, 1 = TILES.
 // Touches no device.  `factors` / `terms`: the filter's separable factors, for the launch that follows.
-static int h16_plan_2d(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, long long in_pitch, const void *d_out,
-                       int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
-{
-    const char *who = kH16Who2D;
-    if (method == 1) { sg_set_error("%s: method 1 (the dense kernel in the reference's summation order) is not served: the reference has no 16-bit form to be identical to", who); return -1; }
-    if (method < 0 || method > 3) { sg_set_error("%s: method %d is not one of 0, 2, 3", who, method); return -1; }
-    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
-        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who, h16_type_name_2d(in_type),
-                     h16_type_name_2d(out_type), in_type, out_type);
-        return -1;
-    }
-    if (!filter || !d_in || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
-    if (!filter_ok(who, filter)) return -1;
-    const int nx = filter->config.half_window_x, ny = filter->config.half_window_y;
-    if (!geometry_ok(who, nx, ny, rows, cols, in_stride, out_stride, boundary)) return -1;
-    if (images == 0) return 0;
-    const int out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
-    const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_in), out0 = reinterpret_cast<uintptr_t>(d_out);
-    if (frames_overlap(in0, 2, in_pitch, in_stride, out0, (size_t)out_elem, out_pitch, out_stride, rows, cols, images)) {
-        sg_set_error("%s: input and output frames overlap (2-D filtering cannot run in place; compared byte-wise)", who);
-        return -1;
-    }
-    // the route (sg_2d_h16_host.hpp).  SAVGOL_HIP_2D_H16_TILES is read at every call, not once: tools/time_2d_h16.py times both routes interleaved in
-    // one process (single-threaded; the header says so).  SAVGOL_HIP_ROLL_TILE is read once, where the fp32 launcher reads it (roll_tiles_on, inside
-    // the predicate); the rule names it as a condition of its own, so the shape carries it too.
-    const char *const tiles_text = getenv("SAVGOL_HIP_2D_H16_TILES");
-    static const bool roll_tile_env = [] { const char *e = getenv("SAVGOL_HIP_ROLL_TILE"); return !e || atoi(e) != 0; }();
-    *terms = sep_factors_cached(&filter->config, factors);
-    FrameShapeH16 shape;
-    shape.rows = rows; shape.cols = cols;
-    shape.in_stride = in_stride; shape.in_pitch = in_pitch; shape.out_stride = out_stride; shape.out_pitch = out_pitch;
-    shape.in_base = in0; shape.out_base = out0; shape.out_elem = out_elem;
-    shape.method = method;
-    shape.x_dominant = sg2d_x_dominant(filter->config.deriv_x, filter->config.deriv_y);
-    shape.additive_tile = *terms > 0 && sg2d_launch_rolling_h16(nx > ny ? nx : ny, *terms, nullptr, factors, filter->scale, 0, nullptr) == 0;
-    shape.roll_tile_switch = roll_tile_env;
-    shape.tiles_switch = !tiles_text || atoi(tiles_text) != 0;
-    return frame_plan_h16(shape) == FRAME_H16_TILES ? 1 : 0;
-}
-
 }  // namespace sg
 
 int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
@@ -648,6 +702,59 @@ int savgol2d_apply_batch_h16(const Savgol2DFilter *filter, const void *d_in, int
         // "not covered": nothing has been enqueued -- the staged route
     }
     return h16_staged_2d(ctx, filter, in, ibf, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, st);
+}
+
+// ---- the 2-D batch call on int16 storage: int16 frames in, int16 or fp32 out, the fp32 call's arithmetic in between (contract: savgol_hip.h) ----
+int savgol2d_apply_batch_i16_route(const Savgol2DFilter *filter, const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch, const void *d_out,
+                                   int out_type, int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method)
+{
+    float factors[sg::SEP_FACTOR_FLOATS];
+    int terms = 0;
+    return sg::i16_plan_2d(filter, d_in, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride, (long long)out_image_pitch, images, (int)boundary,
+                           method, factors, &terms);
+}
+
+int savgol2d_apply_batch_i16(const Savgol2DFilter *filter, const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch, void *d_out, int out_type,
+                             int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method, void *stream)
+{
+    using namespace sg;
+    const char *who = kI16Who2D;
+    const long long in_pitch = (long long)in_image_pitch, out_pitch = (long long)out_image_pitch;
+    float factors[SEP_FACTOR_FLOATS];
+    int terms = 0;
+    // the refusals, in the order the header gives, and the route: decided before anything touches the device
+    const int route = i16_plan_2d(filter, d_in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, factors, &terms);
+    if (route < 0) return -1;
+    if (images == 0) return 0;
+    DeviceCtx *ctx = ctx_get();
+    if (!ctx) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const short *in = reinterpret_cast<const short *>(d_in);
+    const int out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const int nx = filter->config.half_window_x, ny = filter->config.half_window_y, n = nx > ny ? nx : ny;
+    if (route == 1) {
+        Job2DI16 job;
+        memset(&job, 0, sizeof(job));
+        job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
+        job.in_pitch = in_pitch; job.out_pitch = out_pitch;
+        job.nx = nx; job.ny = ny;
+        job.boundary = ((int)boundary == SAVGOL2D_BOUNDARY_VALID || (int)boundary == SAVGOL2D_BOUNDARY_REFLECT) ? (int)boundary : SAVGOL2D_BOUNDARY_CONSTANT;
+        job.out_f32 = out_type == SAVGOL_HIP_F32 ? 1 : 0;
+        // chunks of images as enqueue_frame cuts them for the twin
+        const size_t max_img = ((size_t)1 << 30) / ((size_t)((cols + 63) / 64) * (size_t)(rows + 1)) + 1;
+        int rc = 0;
+        for (size_t i0 = 0; i0 < images && rc == 0; i0 += max_img) {
+            const unsigned ni = (unsigned)(images - i0 < max_img ? images - i0 : max_img);
+            job.in = in + (long long)i0 * in_pitch;
+            job.out = static_cast<unsigned char *>(d_out) + i0 * (size_t)out_pitch * (size_t)out_elem;
+            rc = sg2d_launch_rolling_i16(n, terms, job, factors, filter->scale, ni, st);
+            if (rc == 1 && i0 > 0) rc = -1;                  // cannot happen: the first chunk's answer holds for all
+        }
+        if (rc == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
+        if (rc < 0) return -1;
+        // "not covered": nothing has been enqueued -- the staged route
+    }
+    return i16_staged_2d(ctx, filter, in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, st);
 }
 
 // ---- device entry points of the derivative frames.  Square windows: a separable frame per output, each through enqueue_frame --

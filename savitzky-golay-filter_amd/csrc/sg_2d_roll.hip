@@ -30,7 +30,11 @@
 #ifdef SG_ROLL_H16
 #include "sg_2d_h16.hpp"
 #endif
+#ifdef SG_ROLL_I16
+#include "sg_2d_i16.hpp"
+#endif
 #include "sg_h16.hpp"
+#include "sg_i16.hpp"
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
 
@@ -156,13 +160,23 @@ __device__ __forceinline__ unsigned long long roll_wave_vote(bool p) { return __
 // 16-BIT STORAGE (sg_2d_roll_h16.inc, a build of this file of its own): JOB = Job2DH16, TIN = 16-bit words, TOUT = bytes.  Only load_row and store_row know:
 // a row's quad is one 8-byte load widened exactly, the ring and everything between the two lambdas is the fp32 text below, and the four results are
 // rounded once on their way out.  With JOB = Job2D and float pointers (every fp32 kernel) the text is what it was.
+//
+// INT16 STORAGE (sg_2d_roll_i16.inc, a third build of this file): JOB = Job2DI16, TIN = short, TOUT = short or float -- the storage types are the
+// pointers' own, known when the kernel is compiled.  load_row is one 8-byte load and widen4_i16; store_row issues ONE store of TOUT (int16: narrow4_i16
+// and an 8-byte store; fp32: the fp32 text itself, which a float output pointer simply takes).  An int16 frame holds no NaN and no Inf and nothing a
+// smoothing filter makes of it overflows fp32, so the row's finiteness vote and both cold redo paths are compiled out: a finite frame's bits are those
+// of the text without the test.  Every branch on I16 below is `if constexpr`: the fp32 and the fp16 / bf16 kernels compile to what they were.
 template <int N, int NT, int NOUT, int MODE, bool BOX, bool ACC, int TR = 0, class JOB, class TIN, class TOUT>
 __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, NOUT> &taps, float *mine, const TIN *in, TOUT *const (&outs)[NOUT],
                                           int xload, int yb, int nout, int lane, int xlo, int xhi, int ylo, int yhi)
 {
     typedef Roll<N, ACC, TR> R;
-    constexpr bool H16 = !std::is_same<TIN, float>::value;
+    constexpr bool I16 = std::is_same<TIN, short>::value;                    // int16 rows in; TOUT = short or float
+    constexpr bool I16_NARROW = I16 && std::is_same<TOUT, short>::value;     // ... and int16 rows out
+    constexpr bool H16 = !std::is_same<TIN, float>::value && !I16;
     static_assert(!H16 || (MODE != 0 && TR > 0 && NOUT == 1), "16-bit rows: tile form on vector loads only");
+    static_assert(!I16 || (MODE != 0 && TR > 0 && NOUT == 1 && BOX), "int16 rows: the additive tile form on vector loads only");
+    static_assert(!I16 || std::is_same<TOUT, short>::value || std::is_same<TOUT, float>::value, "int16 rows: int16 or fp32 out");
     static_assert(!BOX || (NT == 2 && NOUT == 1), "the additive form is one output of two terms");
     static_assert(TR == 0 || !ACC, "tiles are plain passes");
     static_assert(!ACC || (NOUT == 1 && !BOX && !R::STRAIGHT), "accumulating passes are single-output launches of the general form");
@@ -192,7 +206,13 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
     const bool reflect = job.boundary == SAVGOL2D_BOUNDARY_REFLECT;
     auto load_row = [&](int r) -> f32x4 {                    // rows past the band are clamped re-reads that are never used
         const TIN *row = in + (long long)fix_row(yb - N + r, job.rows, reflect) * job.in_stride;
-        if constexpr (H16) {                                 // one 8-byte load, widened exactly; the edge strips' remap works on the widened quad
+        if constexpr (I16) {                                 // one 8-byte load and one exact convert per element; the remap as for the 16-bit floats
+            const float4 w = widen4_i16(*reinterpret_cast<const u32x2 *>(row + (EDGE ? qcol : c0)));
+            const f32x4 q = f32x4{w.x, w.y, w.z, w.w};
+            if constexpr (!EDGE) return q;
+            const float nx = fx_w ? q.w : q.x, nw = fx_x ? q.x : q.w;
+            return f32x4{nx, fx_b ? nx : (fx_rev ? q.z : q.y), fx_b ? nx : (fx_rev ? q.y : q.z), nw};
+        } else if constexpr (H16) {                          // one 8-byte load, widened exactly; the edge strips' remap works on the widened quad
             const u32x2 raw = *reinterpret_cast<const u32x2 *>(row + (EDGE ? qcol : c0));
             const f32x2 lo = widen2(raw.x, job.in_bf != 0), hi = widen2(raw.y, job.in_bf != 0);
             const f32x4 q = f32x4{lo.x, lo.y, hi.x, hi.y};
@@ -215,8 +235,9 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
     // 16-bit rows: bytes per stored element, wave-uniform (2, or 4 for fp32 output); every offset below counts it where the fp32 text has its 4
     int es = 4;
     if constexpr (H16) es = job.out_f32 ? 4 : 2;
+    if constexpr (I16_NARROW) es = 2;                        // int16 rows out: the element size is the type's (fp32 out takes the fp32 text)
     unsigned col_off = (out_lane && whole) ? (unsigned)(c0 * 4) : 0x80000000u;
-    if constexpr (H16) col_off = (out_lane && whole) ? (unsigned)(c0 * es) : 0x80000000u;
+    if constexpr (H16 || I16_NARROW) col_off = (out_lane && whole) ? (unsigned)(c0 * es) : 0x80000000u;
     // (their four dword stores go through a per-row descriptor that spans exactly the row's stored range [xlo, xhi): the hardware range
     //  check drops the floats outside it.  One offset register per float, each laundered: left to see that the four offsets are
     //  consecutive, hipcc merges the four dword stores into ONE dwordx4 store, whose range check then passes or fails as a whole --
@@ -225,7 +246,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
     if constexpr (PARTIAL) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if constexpr (H16) { if (out_lane && !whole) pcol_off[j] = (unsigned)((c0 - xlo + j) * es); }
+            if constexpr (H16 || I16_NARROW) { if (out_lane && !whole) pcol_off[j] = (unsigned)((c0 - xlo + j) * es); }
             else if (out_lane && !whole) pcol_off[j] = (unsigned)((c0 - xlo + j) * 4);
             asm volatile("" : "+v"(pcol_off[j]));
         }
@@ -233,7 +254,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
     if constexpr (VEC && R::STRAIGHT) {
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) {
-            if constexpr (H16) rsrc[o] = __builtin_amdgcn_make_buffer_rsrc(outs[o], 0, (int)((long long)job.rows * job.out_stride * es), 0x00020000);
+            if constexpr (H16 || I16_NARROW) rsrc[o] = __builtin_amdgcn_make_buffer_rsrc(outs[o], 0, (int)((long long)job.rows * job.out_stride * es), 0x00020000);
             else rsrc[o] = __builtin_amdgcn_make_buffer_rsrc(outs[o], 0, (int)((long long)job.rows * job.out_stride * 4), 0x00020000);
         }
     }
@@ -262,7 +283,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
             }
             vbp[0] = vb0 - lo2(win[u0]);                     // the row the next output row no longer sees
             vbp[1] = vb1 - hi2(win[u0]);
-            {
+            if constexpr (!I16) {                            // (int16 rows: every sum is finite -- no vote, rowbad stays 0 and the cold paths are not compiled)
                 // The sum must not carry a non-finite value past the row that brought it: NaN - NaN and Inf - Inf leave a NaN behind when that row leaves,
                 // and it would run down the column until the next re-seed.  A lane whose carried sum is not finite (a special is, or just was, in its
                 // window; or a finite overflow, which only re-seeds) takes the plain sum of the next window's first 2N rows from the ring instead --
@@ -392,7 +413,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
             // 0 x NaN = NaN.  Either needs a special in one of the row's two LDS rows, which is what the vertical pass's vote says.  Then a result that is not
             // finite is summed again over its own window, both units from the floats their LDS rows still hold: a[k] = qx[k].x times float D + j + k of
             // term 0's row, plus the plain sum of floats lo + j .. hi + j of term 1's.
-            if (__builtin_expect(rowbad[par] != 0, 0)) {
+            if constexpr (!I16) if (__builtin_expect(rowbad[par] != 0, 0)) {
                 const float *const w0 = rd + ((par * NOUT + o) * NT + 0) * R::BUFW, *const w1 = rd + ((par * NOUT + o) * NT + 1) * R::BUFW;
                 auto direct = [&](float &rj, int j) {                // summed in place under the lane mask: the cold path holds no register of its own
                     if (roll_nonfinite(rj)) {
@@ -488,6 +509,21 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
             // or without the row part added) is fixed for the item; the row part is wave-uniform: one v_add per row.  A row
             // nobody stores selects the empty descriptor (scalar select).
             const bool keep_row = yo >= ylo && yo < yhi && yo < yend;                     // uniform
+            if constexpr (I16_NARROW) {
+                // int16 rows out: the four results converted once (round to nearest even, saturate, NaN -> 0), two dwords, ONE 8-byte store -- the
+                // output's type is the kernel's own, so there is no second store to drop.  (fp32 rows out take the fp32 text below as it stands.)
+                const u32x2 pk = narrow4_i16(float4{r[0].x, r[0].y, r[1].x, r[1].y});
+                __builtin_amdgcn_raw_buffer_store_b64(pk, keep_row ? rsrc[o] : rsrc_none, (int)(col_off + (unsigned)(yo * job.out_stride * 2)), 0, 2 /* nt */);
+                if constexpr (PARTIAL) {
+                    // VALID's partial quads: four range-checked 2-byte stores through the row's descriptor over [xlo, xhi) elements
+                    const unsigned short h[4] = {(unsigned short)(pk.x & 0xffffu), (unsigned short)(pk.x >> 16), (unsigned short)(pk.y & 0xffffu), (unsigned short)(pk.y >> 16)};
+                    const __amdgpu_buffer_rsrc_t prow = __builtin_amdgcn_make_buffer_rsrc(outs[o] + ((long long)yo * job.out_stride + xlo), 0,
+                                                                                          keep_row ? (xhi - xlo) * 2 : 0, 0x00020000);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_buffer_store_b16(h[j], prow, (int)pcol_off[j], 0, 0);
+                }
+                return;
+            }
             if constexpr (H16) {
                 // The storage type of the output is wave-uniform, and a branch on it would be a branch in the tile: BOTH stores are issued, the one of
                 // the other type through the empty descriptor.  16 -> 16 bit: the four results rounded once to nearest even, two dwords, ONE 8-byte
@@ -964,6 +1000,9 @@ static int dispatch_roll2(int n, int terms, const Job2D &job, const float *f0, f
 // The 16-bit-storage build of this file (Makefile, ROLL_H16_RULE): the additive tile on 16-bit rows and its launcher under the name SEP_ROLL_FN, in
 // place of the fp32 entry points.  Everything above is shared text; no fp32 kernel is instantiated in this build.
 #include "sg_2d_roll_h16.inc"
+#elif defined(SG_ROLL_I16)
+// The int16-storage build (Makefile, ROLL_I16_RULE): the additive tile on int16 rows, the storage types at compile time, under the name SEP_ROLL_FN.
+#include "sg_2d_roll_i16.inc"
 #else
 // 0 = launched, 1 = this object does not cover the case (half window outside SEP_ROLL_MIN_N..SEP_ROLL_MAX_N, no
 // definite parity).  Built once per half-window group (Makefile), each under its own name SEP_ROLL_FN.
