@@ -15,10 +15,7 @@
 #include <vector>
 
 #include "sg_k1d_host.hpp"
-#include "sg_k1d_h16_host.hpp"
-#include "sg_k1d_i16_host.hpp"
-#include "sg_k1d_multi_h16_host.hpp"
-#include "sg_k1d_multi_i16_host.hpp"
+#include "sg_k1d_st16_host.hpp"
 #include "sg_k1d_strided_multi_launch.hpp"
 #include "sg_runtime.hpp"
 
@@ -197,7 +194,7 @@ constexpr size_t LAUNCH_MAX_LENGTH = (size_t)1 << 30;
 // ------------------------------------------------------------------------------------------------
 // The decisions every device route shares, each stated here and nowhere else: the argument checks, what a call stores where
 // (CallShape), what one output adds to it (OutputPart), which kernel family and tile width a call takes, how a batch is cut
-// into launches.  enqueue_multi, enqueue_h16 and enqueue_multi_h16 promise the bits of enqueue_batch<float>: they hold because all four ask these.
+// into launches.  enqueue_multi, enqueue_st16 and enqueue_multi_st16 promise the bits of enqueue_batch<float>: they hold because all four ask these.
 // ------------------------------------------------------------------------------------------------
 
 // The argument checks of a batch call, in this order.  `too_long`: the refusal text (who, length) of a route that does not serve
@@ -721,54 +718,108 @@ int enqueue_multi(const char *who, const SavgolFilter *const *filters, int count
 }
 
 // ------------------------------------------------------------------------------------------------
-// 16-bit storage (savgol_apply[_valid]_batch_h16): fp16 / bf16 rows in, the same type or fp32 out, on the kernels of sg_k1d_h16.hpp.  The job is the
-// one enqueue_batch<float> builds for the widened input under SAVGOL_BATCH_TILE_NARROW, field for field -- same kernel family (block moments where
-// the fp32 call takes them), same stored range, same centring, same edge items -- plus the two storage types; pitches and alignment are counted in
-// elements of their own buffer.  Every refusal comes before the first device call.
+// 16-bit storage, two families (sg_k1d_st16_host.hpp): fp16 / bf16 rows in, the same type or fp32 out (savgol_apply[_valid]_batch_h16), and int16
+// rows in, int16 or fp32 out (savgol_apply[_valid]_batch_i16), on the kernels of sg_k1d_st16.hpp.  The job is the one enqueue_batch<float> builds for
+// the widened input under SAVGOL_BATCH_TILE_NARROW, field for field -- same kernel family (block moments where the fp32 call takes them), same stored
+// range, same centring, same edge items -- plus the family's storage types; pitches and alignment are counted in elements of their own buffer (2 -> 2
+// or 4 bytes).  ONE single route (enqueue_st16) and ONE fused route (enqueue_multi_st16) serve both families; what the families differ in is their
+// host-side description (H16Host, I16Host):
+//   Types          the job's storage fields, with the family's noun in the error texts (Types::NOUN);
+//   TOO_LONG       check_rows' refusal text (who, length);
+//   types_served   the refusal of a storage pair (h16) or an output type (i16) the family does not serve;
+//   single_linked  whether the single kernels can be reached: int16 has ONE weak entry point, which a build without the kernel objects leaves null
+//                  ("object not linked"); h16 reaches its objects directly and has no such check;
+//   launch         one launch of the single kernels, plain or block-moment;
+//   multi_entry    the ONE weak entry point of the fused kernels, null where the objects are not linked.
+// Every refusal comes before the first device call.
 // ------------------------------------------------------------------------------------------------
 const char *storage_name(int t)
 {
     return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown";
 }
+const char *i16_storage_name(int t)
+{
+    return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_I16 ? "i16" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown";
+}
 
-// check_rows' refusal text of both 16-bit routes (who, length)
-constexpr const char *H16_TOO_LONG = "%s: channels longer than 2^30 samples (%zu) are not served on 16-bit storage";
-
-// what both 16-bit routes refuse first, in this order: the flags they do not serve, then the storage pair
-bool h16_call_served(const char *who, unsigned flags, int in_type, int out_type)
+// what every 16-bit-storage route refuses first, in this order: the flags it does not serve
+bool st16_flags_served(const char *who, unsigned flags, const char *noun)
 {
     if (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) {
-        sg_set_error("%s: SAVGOL_BATCH_REFERENCE_SUMMATION is not served on 16-bit storage (the reference has no 16-bit form to be identical to)", who);
+        sg_set_error("%s: SAVGOL_BATCH_REFERENCE_SUMMATION is not served on %s storage (the reference has no %s form to be identical to)", who, noun, noun);
         return false;
     }
-    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on 16-bit storage (the call runs the narrow tile)", who); return false; }
+    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on %s storage (the call runs the narrow tile)", who, noun); return false; }
     if (flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64)) {
         sg_set_error("%s: flags 0x%x belong to other calls (BOUNDARY_AWARE: strided calls, MOMENT_F64: fp64 calls)", who, flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64));
         return false;
     }
     if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return false; }
-    const bool in16 = in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16;
-    if (!in16 || !(out_type == in_type || out_type == SAVGOL_HIP_F32)) {
-        sg_set_error("%s: storage pair %s -> %s (%d -> %d) is not served (f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32; f32 -> f32 is savgol_apply_batch_f32)", who,
-                     storage_name(in_type), storage_name(out_type), in_type, out_type);
-        return false;
-    }
     return true;
 }
 
-int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
-                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+struct H16Host {
+    typedef sg::H16Types Types;
+    static constexpr const char *TOO_LONG = "%s: channels longer than 2^30 samples (%zu) are not served on 16-bit storage";
+    static bool types_served(const char *who, const Types &t)
+    {
+        const int in_type = (int)t.in_type, out_type = (int)t.out_type;
+        const bool in16 = in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16;
+        if (!in16 || !(out_type == in_type || out_type == SAVGOL_HIP_F32)) {
+            sg_set_error("%s: storage pair %s -> %s (%d -> %d) is not served (f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32; f32 -> f32 is savgol_apply_batch_f32)", who,
+                         storage_name(in_type), storage_name(out_type), in_type, out_type);
+            return false;
+        }
+        return true;
+    }
+    static bool single_linked() { return true; }
+    static int launch(int n, const sg::JobH16 &job, const FilterPlan *plan, const float *d_moment, unsigned blocks, hipStream_t st)
+    {
+        return d_moment ? MOMENT_H16[terms_slot(plan->moment_terms)](n, &job, d_moment, blocks, st) : sg::launch_h16(n, job, plan->taps32, blocks, st);
+    }
+    static auto multi_entry() { return sg1d_launch_multi_h16; }
+};
+
+struct I16Host {
+    typedef sg::I16Types Types;
+    static constexpr const char *TOO_LONG = "%s: channels longer than 2^30 samples (%zu) are not served on int16 storage";
+    static bool types_served(const char *who, const Types &t)
+    {
+        const int out_type = (int)t.out_type;
+        if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
+            sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, i16_storage_name(out_type), out_type);
+            return false;
+        }
+        return true;
+    }
+    static bool single_linked() { return sg1d_launch_i16 != nullptr; }
+    static int launch(int n, const sg::JobI16 &job, const FilterPlan *plan, const float *d_moment, unsigned blocks, hipStream_t st)
+    {
+        return sg1d_launch_i16(n, d_moment ? plan->moment_terms : 0, &job, &plan->taps32, d_moment, blocks, st);
+    }
+    static auto multi_entry() { return sg1d_launch_multi_i16; }
+};
+
+// The single call.  The checks, in this order (the first fault wins), all before the first device call:
+//   1. flags: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the storage pair / the output type;
+//   3. check_rows: NULL pointer, length < window, channels beyond 2^30 samples, pitches;   (zero channels: 0, nothing enqueued)
+//   4. input and output rows that share a byte;   5. the kernel objects are linked (int16);   6. a usable device.
+template <typename F>
+int enqueue_st16(const char *who, const SavgolFilter *f, const void *d_in, void *d_out, const typename F::Types &types, size_t channels, size_t length,
+                 size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
 {
-    if (!h16_call_served(who, flags, in_type, out_type)) return -1;
-    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, H16_TOO_LONG)) return -1;
+    const char *noun = F::Types::NOUN;
+    if (!st16_flags_served(who, flags, noun) || !F::types_served(who, types)) return -1;
+    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, F::TOO_LONG)) return -1;
     if (channels == 0) return 0;
     const int n = f->config.half_window;
     const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
-    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
+    const size_t ib = 2, ob = types.out_type == SAVGOL_HIP_F32 ? 4 : 2;  // bytes per element
     if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_out, out_ld * ob, out_len * ob, channels)) {
-        sg_set_error("%s: d_in and d_out overlap (the 16-bit-storage call does not run in place: input and output rows may not share a byte)", who);
+        sg_set_error("%s: d_in and d_out overlap (the %s-storage call does not run in place: input and output rows may not share a byte)", who, noun);
         return -1;
     }
+    if (!F::single_linked()) { sg_set_error("%s: the %s-storage kernels are not part of this build (object not linked)", who, noun); return -1; }
 
     DeviceCtx *ctx = sg::ctx_get();
     if (!ctx) return -1;
@@ -779,124 +830,46 @@ int enqueue_h16(const char *who, const SavgolFilter *f, const void *d_in, int in
     const float *d_moment = (want_moment && plan->moment_terms > 0) ? plan->d_moment : nullptr;
 
     constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
-    sg::JobH16 jh;
-    memset(&jh, 0, sizeof(jh));
-    sg::Job1D &job = jh.base;
+    sg::JobSt16<typename F::Types> js;
+    memset(&js, 0, sizeof(js));
+    sg::Job1D &job = js.base;
     job_init(job, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
     job_set_output(job, output_part(f, shape, flags, true, rows_vector_aligned(d_out, out_ld, ob, E, shape.out_shift)), shape.want_edges ? plan->d_edges : nullptr);
-    jh.in_type = (unsigned)in_type;
-    jh.out_type = (unsigned)out_type;
+    static_cast<typename F::Types &>(js) = types;
     const unsigned tpc = job.tiles_per_channel;
     for (ChannelGroups g{channels, launch_max_channels(tpc, 2)}; g.next();) {
         job.in = static_cast<const char *>(d_in) + g.c0 * in_ld * ib;
         job.out = static_cast<char *>(d_out) + g.c0 * out_ld * ob;
         job.total_tiles = (unsigned)(g.nc * tpc);
         job.edge_items = shape.want_edges ? (unsigned)(2 * g.nc) : 0u;
-        const unsigned blocks = grid_blocks(job.total_tiles + job.edge_items);
-        const int rc = d_moment ? MOMENT_H16[terms_slot(plan->moment_terms)](n, &jh, d_moment, blocks, st) : sg::launch_h16(n, jh, plan->taps32, blocks, st);
-        if (rc != 0) return -1;
+        if (F::launch(n, js, plan, d_moment, grid_blocks(job.total_tiles + job.edge_items), st) != 0) return -1;
     }
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// int16 storage (savgol_apply[_valid]_batch_i16): int16 rows in, int16 or fp32 out, on the kernels of sg_k1d_i16.hpp.  enqueue_h16's job, field for
-// field -- the one enqueue_batch<float> builds for the widened input under SAVGOL_BATCH_TILE_NARROW -- with element sizes 2 -> 2 or 4, plus the output
-// type.  The checks, in this order (the first fault wins), all before the first device call:
-//   1. flags: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the output type;
-//   3. check_rows: NULL pointer, length < window, channels beyond 2^30 samples, pitches;   (zero channels: 0, nothing enqueued)
-//   4. input and output rows that share a byte;   5. the kernel objects are linked;   6. a usable device.
-// ------------------------------------------------------------------------------------------------
-const char *i16_storage_name(int t)
-{
-    return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_I16 ? "i16" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown";
-}
-
-constexpr const char *I16_TOO_LONG = "%s: channels longer than 2^30 samples (%zu) are not served on int16 storage";
-
-// what both int16 routes refuse first, in this order: the flags they do not serve, then the output type
-bool i16_call_served(const char *who, unsigned flags, int out_type)
-{
-    if (flags & SAVGOL_BATCH_REFERENCE_SUMMATION) {
-        sg_set_error("%s: SAVGOL_BATCH_REFERENCE_SUMMATION is not served on int16 storage (the reference has no int16 form to be identical to)", who);
-        return false;
-    }
-    if (flags & SAVGOL_BATCH_TILE_WIDE) { sg_set_error("%s: SAVGOL_BATCH_TILE_WIDE is not served on int16 storage (the call runs the narrow tile)", who); return false; }
-    if (flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64)) {
-        sg_set_error("%s: flags 0x%x belong to other calls (BOUNDARY_AWARE: strided calls, MOMENT_F64: fp64 calls)", who, flags & (SAVGOL_BATCH_BOUNDARY_AWARE | SAVGOL_BATCH_MOMENT_F64));
-        return false;
-    }
-    if (flags & ~(unsigned)(SAVGOL_BATCH_PLAIN_SUMMATION | SAVGOL_BATCH_TILE_NARROW | SAVGOL_BATCH_CORRECT_LEADING_EDGE)) { sg_set_error("%s: bad flags 0x%x", who, flags); return false; }
-    if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
-        sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, i16_storage_name(out_type), out_type);
-        return false;
-    }
-    return true;
-}
-
-int enqueue_i16(const char *who, const SavgolFilter *f, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
-                size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
-{
-    if (!i16_call_served(who, flags, out_type)) return -1;
-    if (!check_rows(who, f, d_in, d_out, length, in_ld, out_ld, variant, I16_TOO_LONG)) return -1;
-    if (channels == 0) return 0;
-    const int n = f->config.half_window;
-    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
-    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
-    if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_out, out_ld * ob, out_len * ob, channels)) {
-        sg_set_error("%s: d_in and d_out overlap (the int16-storage call does not run in place: input and output rows may not share a byte)", who);
-        return -1;
-    }
-    if (!sg1d_launch_i16) { sg_set_error("%s: the int16-storage kernels are not part of this build (object not linked)", who); return -1; }
-
-    DeviceCtx *ctx = sg::ctx_get();
-    if (!ctx) return -1;
-    const CallShape shape = call_shape(f, variant, length);
-    const bool want_moment = takes_moment32(f, n, flags);
-    const FilterPlan *plan = plan_get(ctx, f, (shape.want_edges ? NEED_EDGES : 0u) | (want_moment ? NEED_MOMENT : 0u));
-    if (!plan) return -1;
-    const float *d_moment = (want_moment && plan->moment_terms > 0) ? plan->d_moment : nullptr;
-
-    constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
-    sg::JobI16 ji;
-    memset(&ji, 0, sizeof(ji));
-    sg::Job1D &job = ji.base;
-    job_init(job, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
-    job_set_output(job, output_part(f, shape, flags, true, rows_vector_aligned(d_out, out_ld, ob, E, shape.out_shift)), shape.want_edges ? plan->d_edges : nullptr);
-    ji.out_type = (unsigned)out_type;
-    const unsigned tpc = job.tiles_per_channel;
-    for (ChannelGroups g{channels, launch_max_channels(tpc, 2)}; g.next();) {
-        job.in = reinterpret_cast<const char *>(d_in) + g.c0 * in_ld * ib;
-        job.out = static_cast<char *>(d_out) + g.c0 * out_ld * ob;
-        job.total_tiles = (unsigned)(g.nc * tpc);
-        job.edge_items = shape.want_edges ? (unsigned)(2 * g.nc) : 0u;
-        if (sg1d_launch_i16(n, d_moment ? plan->moment_terms : 0, &ji, &plan->taps32, d_moment, grid_blocks(job.total_tiles + job.edge_items), st) != 0) return -1;
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Several filters on one read of 16-bit rows (savgol_apply[_valid]_multi_batch_h16): enqueue_multi's job built with enqueue_h16's storage rules, on
-// sg1d_multi_h16_kernel (sg_k1d_multi_h16.hpp).  The narrow tile and the plain summation are implied, so every output fuses: 2 or 3 outputs are one
-// launch, 4 are two launches of two, 1 is the 16-bit single call with SAVGOL_BATCH_PLAIN_SUMMATION.  The checks, in this order (the first fault wins):
-//   1. flags, as enqueue_h16: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the storage pair;
+// Several filters on one read of 16-bit rows (savgol_apply[_valid]_multi_batch_h16 / _i16): enqueue_multi's job built with enqueue_st16's storage
+// rules, on the kernels of sg_k1d_multi_st16.hpp.  The narrow tile and the plain summation are implied, so every output fuses: 2 or 3 outputs are one
+// launch, 4 are two launches of two, 1 is the family's single call with SAVGOL_BATCH_PLAIN_SUMMATION.  The checks, in this order (the first fault wins):
+//   1. flags, as enqueue_st16: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the storage pair / the output type;
 //   3. NULL filters / d_outs / d_in;   4. count;   5. a NULL or malformed entry, k ascending;   6. half_window, then boundary, of filters[k] against
 //   filters[0], k ascending;   7. check_rows: length < window, channels beyond 2^30 samples, pitches;   (zero channels: 0, nothing enqueued)
-//   8. shared bytes, k ascending: d_outs[k] against d_in, then against d_outs[j], j < k;   9. the kernel objects are linked;   10. a usable device.
-// ------------------------------------------------------------------------------------------------
-int enqueue_multi_h16(const char *who, const SavgolFilter *const *filters, int count, const void *d_in, int in_type, void *const *d_outs, int out_type,
-                      size_t channels, size_t length, size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
+//   8. shared bytes, k ascending: d_outs[k] against d_in, then against d_outs[j], j < k;   (count 1: the single call from here)
+//   9. the kernel objects are linked;   10. a usable device.
+template <typename F>
+int enqueue_multi_st16(const char *who, const SavgolFilter *const *filters, int count, const void *d_in, void *const *d_outs, const typename F::Types &types,
+                       size_t channels, size_t length, size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
 {
-    if (!h16_call_served(who, flags, in_type, out_type)) return -1;
+    const char *noun = F::Types::NOUN;
+    if (!st16_flags_served(who, flags, noun) || !F::types_served(who, types)) return -1;
     if (!filters || !d_outs || !d_in) { sg_set_error("%s: NULL pointer", who); return -1; }
     if (count < 1 || count > SAVGOL_MULTI_MAX_FILTERS) { sg_set_error("%s: count %d outside 1..%d", who, count, SAVGOL_MULTI_MAX_FILTERS); return -1; }
     if (!multi_filters_match(who, filters, d_outs, count)) return -1;
     const SavgolFilter *f0 = filters[0];
     const int n = f0->config.half_window;
-    if (!check_rows(who, f0, d_in, d_outs[0], length, in_ld, out_ld, variant, H16_TOO_LONG)) return -1;
+    if (!check_rows(who, f0, d_in, d_outs[0], length, in_ld, out_ld, variant, F::TOO_LONG)) return -1;
     if (channels == 0) return 0;
     const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
-    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
+    const size_t ib = 2, ob = types.out_type == SAVGOL_HIP_F32 ? 4 : 2;  // bytes per element
     for (int k = 0; k < count; ++k) {
         if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_outs[k], out_ld * ob, out_len * ob, channels)) {
             sg_set_error("%s: d_outs[%d] overlaps d_in (the multi-output call does not run in place: input and output rows may not share a byte)", who, k);
@@ -908,19 +881,19 @@ int enqueue_multi_h16(const char *who, const SavgolFilter *const *filters, int c
                 return -1;
             }
     }
-    if (count == 1) return enqueue_h16(who, f0, d_in, in_type, d_outs[0], out_type, channels, length, in_ld, out_ld, variant, st, flags | SAVGOL_BATCH_PLAIN_SUMMATION);
-    if (!sg1d_launch_multi_h16) { sg_set_error("%s: the 16-bit multi-output kernels are not part of this build (object not linked)", who); return -1; }
+    if (count == 1) return enqueue_st16<F>(who, f0, d_in, d_outs[0], types, channels, length, in_ld, out_ld, variant, st, flags | SAVGOL_BATCH_PLAIN_SUMMATION);
+    const auto launch = F::multi_entry();
+    if (!launch) { sg_set_error("%s: the %s multi-output kernels are not part of this build (object not linked)", who, noun); return -1; }
 
     DeviceCtx *ctx = sg::ctx_get();
     if (!ctx) return -1;
     const CallShape shape = call_shape(f0, variant, length);
     constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
-    sg::JobMultiH16 jh;
-    memset(&jh, 0, sizeof(jh));
-    sg::JobMulti1D &jm = jh.multi;
+    sg::JobMultiSt16<typename F::Types> js;
+    memset(&js, 0, sizeof(js));
+    sg::JobMulti1D &jm = js.multi;
     job_init(jm.base, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
-    jh.in_type = (unsigned)in_type;
-    jh.out_type = (unsigned)out_type;
+    static_cast<typename F::Types &>(js) = types;
     const unsigned tpc = jm.base.tiles_per_channel;
     const int all[SAVGOL_MULTI_MAX_FILTERS] = {0, 1, 2, 3};
 
@@ -931,79 +904,12 @@ int enqueue_multi_h16(const char *who, const SavgolFilter *const *filters, int c
         if (!multi_launch_outputs(ctx, jm, taps, filters, d_outs, all + g0, K, shape, flags, out_ld, ob)) return -1;
         // the edge items of every output counted
         for (ChannelGroups g{channels, launch_max_channels(tpc, 2 * (unsigned)K)}; g.next();) {
-            sg::JobMultiH16 j = jh;
+            sg::JobMultiSt16<typename F::Types> j = js;
             j.multi.base.in = static_cast<const char *>(d_in) + g.c0 * in_ld * ib;
             for (int o = 0; o < K; ++o) j.multi.out[o] = static_cast<char *>(jm.out[o]) + g.c0 * out_ld * ob;
             j.multi.base.total_tiles = (unsigned)(g.nc * tpc);
             j.multi.base.edge_items = shape.want_edges ? (unsigned)(2 * g.nc * (size_t)K) : 0u;
-            if (sg1d_launch_multi_h16(n, K, &j, &taps, grid_blocks(j.multi.base.total_tiles + j.multi.base.edge_items), st) != 0) return -1;
-        }
-        g0 += K;
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Several filters on one read of int16 rows (savgol_apply[_valid]_multi_batch_i16): enqueue_multi_h16's route with enqueue_i16's storage rules, on
-// sg1d_multi_i16_kernel (sg_k1d_multi_i16.hpp).  The narrow tile and the plain summation are implied, so every output fuses: 2 or 3 outputs are one
-// launch, 4 are two launches of two, 1 is the int16 single call with SAVGOL_BATCH_PLAIN_SUMMATION.  The checks, in this order (the first fault wins):
-//   1. flags, as enqueue_i16: REFERENCE_SUMMATION, TILE_WIDE, flags of other calls, unknown bits;   2. the output type;
-//   3. NULL filters / d_outs / d_in;   4. count;   5. a NULL or malformed entry, k ascending;   6. half_window, then boundary, of filters[k] against
-//   filters[0], k ascending;   7. check_rows: length < window, channels beyond 2^30 samples, pitches;   (zero channels: 0, nothing enqueued)
-//   8. shared bytes, k ascending: d_outs[k] against d_in, then against d_outs[j], j < k;   9. the kernel objects are linked;   10. a usable device.
-// ------------------------------------------------------------------------------------------------
-int enqueue_multi_i16(const char *who, const SavgolFilter *const *filters, int count, const int16_t *d_in, void *const *d_outs, int out_type,
-                      size_t channels, size_t length, size_t in_ld, size_t out_ld, Variant variant, hipStream_t st, unsigned flags)
-{
-    if (!i16_call_served(who, flags, out_type)) return -1;
-    if (!filters || !d_outs || !d_in) { sg_set_error("%s: NULL pointer", who); return -1; }
-    if (count < 1 || count > SAVGOL_MULTI_MAX_FILTERS) { sg_set_error("%s: count %d outside 1..%d", who, count, SAVGOL_MULTI_MAX_FILTERS); return -1; }
-    if (!multi_filters_match(who, filters, d_outs, count)) return -1;
-    const SavgolFilter *f0 = filters[0];
-    const int n = f0->config.half_window;
-    if (!check_rows(who, f0, d_in, d_outs[0], length, in_ld, out_ld, variant, I16_TOO_LONG)) return -1;
-    if (channels == 0) return 0;
-    const size_t out_len = (variant == VALID) ? length - 2 * (size_t)n : length;
-    const size_t ib = 2, ob = out_type == SAVGOL_HIP_F32 ? 4 : 2;        // bytes per element
-    for (int k = 0; k < count; ++k) {
-        if (rows_overlap_bytes((uintptr_t)d_in, in_ld * ib, length * ib, (uintptr_t)d_outs[k], out_ld * ob, out_len * ob, channels)) {
-            sg_set_error("%s: d_outs[%d] overlaps d_in (the multi-output call does not run in place: input and output rows may not share a byte)", who, k);
-            return -1;
-        }
-        for (int j = 0; j < k; ++j)
-            if (rows_overlap_bytes((uintptr_t)d_outs[j], out_ld * ob, out_len * ob, (uintptr_t)d_outs[k], out_ld * ob, out_len * ob, channels)) {
-                sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap", who, j, k);
-                return -1;
-            }
-    }
-    if (count == 1) return enqueue_i16(who, f0, d_in, d_outs[0], out_type, channels, length, in_ld, out_ld, variant, st, flags | SAVGOL_BATCH_PLAIN_SUMMATION);
-    if (!sg1d_launch_multi_i16) { sg_set_error("%s: the int16 multi-output kernels are not part of this build (object not linked)", who); return -1; }
-
-    DeviceCtx *ctx = sg::ctx_get();
-    if (!ctx) return -1;
-    const CallShape shape = call_shape(f0, variant, length);
-    constexpr unsigned E = 4;                                            // elements the kernels move as one vector, whatever the storage type
-    sg::JobMultiI16 ji;
-    memset(&ji, 0, sizeof(ji));
-    sg::JobMulti1D &jm = ji.multi;
-    job_init(jm.base, shape, length, in_ld, out_ld, 64u * (unsigned)sg::VPL_NARROW * E, rows_vector_aligned(d_in, in_ld, ib, E));
-    ji.out_type = (unsigned)out_type;
-    const unsigned tpc = jm.base.tiles_per_channel;
-    const int all[SAVGOL_MULTI_MAX_FILTERS] = {0, 1, 2, 3};
-
-    // launches of 3, 2 or 2 + 2 outputs
-    for (int g0 = 0; g0 < count;) {
-        const int K = (count - g0 == 4) ? 2 : (count - g0);
-        sg::TapsMulti taps;
-        if (!multi_launch_outputs(ctx, jm, taps, filters, d_outs, all + g0, K, shape, flags, out_ld, ob)) return -1;
-        // the edge items of every output counted
-        for (ChannelGroups g{channels, launch_max_channels(tpc, 2 * (unsigned)K)}; g.next();) {
-            sg::JobMultiI16 j = ji;
-            j.multi.base.in = reinterpret_cast<const char *>(d_in) + g.c0 * in_ld * ib;
-            for (int o = 0; o < K; ++o) j.multi.out[o] = static_cast<char *>(jm.out[o]) + g.c0 * out_ld * ob;
-            j.multi.base.total_tiles = (unsigned)(g.nc * tpc);
-            j.multi.base.edge_items = shape.want_edges ? (unsigned)(2 * g.nc * (size_t)K) : 0u;
-            if (sg1d_launch_multi_i16(n, K, &j, &taps, grid_blocks(j.multi.base.total_tiles + j.multi.base.edge_items), st) != 0) return -1;
+            if (launch(n, K, &j, &taps, grid_blocks(j.multi.base.total_tiles + j.multi.base.edge_items), st) != 0) return -1;
         }
         g0 += K;
     }
@@ -1270,52 +1176,52 @@ int savgol_apply_valid_multi_batch_f32(const SavgolFilter *const *filters, int c
 int savgol_apply_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
                            size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_h16("savgol_apply_batch_h16", filter, d_in, in_type, d_out, out_type, channels, length, in_ld, out_ld, FULL, static_cast<hipStream_t>(stream), flags);
+    return enqueue_st16<H16Host>("savgol_apply_batch_h16", filter, d_in, d_out, {(unsigned)in_type, (unsigned)out_type}, channels, length, in_ld, out_ld, FULL, static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_valid_batch_h16(const SavgolFilter *filter, const void *d_in, int in_type, void *d_out, int out_type, size_t channels, size_t length,
                                  size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_h16("savgol_apply_valid_batch_h16", filter, d_in, in_type, d_out, out_type, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
+    return enqueue_st16<H16Host>("savgol_apply_valid_batch_h16", filter, d_in, d_out, {(unsigned)in_type, (unsigned)out_type}, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
                            size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_i16("savgol_apply_batch_i16", filter, d_in, d_out, out_type, channels, length, in_ld, out_ld, FULL, static_cast<hipStream_t>(stream), flags);
+    return enqueue_st16<I16Host>("savgol_apply_batch_i16", filter, d_in, d_out, {(unsigned)out_type}, channels, length, in_ld, out_ld, FULL, static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_valid_batch_i16(const SavgolFilter *filter, const int16_t *d_in, void *d_out, int out_type, size_t channels, size_t length,
                                  size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_i16("savgol_apply_valid_batch_i16", filter, d_in, d_out, out_type, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
+    return enqueue_st16<I16Host>("savgol_apply_valid_batch_i16", filter, d_in, d_out, {(unsigned)out_type}, channels, length, in_ld, out_ld, VALID, static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_multi_batch_h16(const SavgolFilter *const *filters, int count, const void *d_in, int in_type, void *const *d_outs, int out_type, size_t channels,
                                  size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_multi_h16("savgol_apply_multi_batch_h16", filters, count, d_in, in_type, d_outs, out_type, channels, length, in_ld, out_ld, FULL,
+    return enqueue_multi_st16<H16Host>("savgol_apply_multi_batch_h16", filters, count, d_in, d_outs, {(unsigned)in_type, (unsigned)out_type}, channels, length, in_ld, out_ld, FULL,
                              static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_valid_multi_batch_h16(const SavgolFilter *const *filters, int count, const void *d_in, int in_type, void *const *d_outs, int out_type, size_t channels,
                                        size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_multi_h16("savgol_apply_valid_multi_batch_h16", filters, count, d_in, in_type, d_outs, out_type, channels, length, in_ld, out_ld, VALID,
+    return enqueue_multi_st16<H16Host>("savgol_apply_valid_multi_batch_h16", filters, count, d_in, d_outs, {(unsigned)in_type, (unsigned)out_type}, channels, length, in_ld, out_ld, VALID,
                              static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_multi_batch_i16(const SavgolFilter *const *filters, int count, const int16_t *d_in, void *const *d_outs, int out_type, size_t channels,
                                  size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_multi_i16("savgol_apply_multi_batch_i16", filters, count, d_in, d_outs, out_type, channels, length, in_ld, out_ld, FULL,
+    return enqueue_multi_st16<I16Host>("savgol_apply_multi_batch_i16", filters, count, d_in, d_outs, {(unsigned)out_type}, channels, length, in_ld, out_ld, FULL,
                              static_cast<hipStream_t>(stream), flags);
 }
 
 int savgol_apply_valid_multi_batch_i16(const SavgolFilter *const *filters, int count, const int16_t *d_in, void *const *d_outs, int out_type, size_t channels,
                                        size_t length, size_t in_ld, size_t out_ld, unsigned flags, void *stream)
 {
-    return enqueue_multi_i16("savgol_apply_valid_multi_batch_i16", filters, count, d_in, d_outs, out_type, channels, length, in_ld, out_ld, VALID,
+    return enqueue_multi_st16<I16Host>("savgol_apply_valid_multi_batch_i16", filters, count, d_in, d_outs, {(unsigned)out_type}, channels, length, in_ld, out_ld, VALID,
                              static_cast<hipStream_t>(stream), flags);
 }
 

@@ -338,7 +338,7 @@ __device__ __forceinline__ void sg1d_edge_item(const JobStrided &job, unsigned i
 
 // ---------------------------------------------------------------------------------------------
 // The pieces of the tile algorithm that every tile kernel shares -- sg1d_tile_body below, sg1d_multi_body (sg_k1d_multi.hpp) and
-// sg1d_h16_body (sg_k1d_h16.hpp) are these in calls, each with its own inner product between them.  The fused and the 16-bit calls promise
+// sg1d_st16_body (sg_k1d_st16.hpp) are these in calls, each with its own inner product between them.  The fused and the 16-bit calls promise
 // the bits of the fp32 single call: one definition of each staging / centring / finishing rule is what keeps that promise on the device.
 // ---------------------------------------------------------------------------------------------
 
@@ -390,7 +390,7 @@ struct SlabRows {
 };
 
 // How rows are stored in memory, for the first and the last hop of a tile: the element type, the raw vector that carries one slab vector's
-// E samples, and the steps between them and the slab's T / VT.  Rows of the slab's own type (fp32, fp64) move as they are; sg_k1d_h16.hpp has
+// E samples, and the steps between them and the slab's T / VT.  Rows of the slab's own type (fp32, fp64) move as they are; sg_k1d_st16.hpp has
 // the 16-bit storage types.
 template <typename T>
 struct SameStorage {

@@ -1,4 +1,4 @@
-"""GPU tests of the 16-bit-storage 1-D batch call (savgol_apply[_valid]_batch_h16, sg_k1d_h16.hpp).  The contract: the output equals, bit for bit, the
+"""GPU tests of the 16-bit-storage 1-D batch call (savgol_apply[_valid]_batch_h16, sg_k1d_st16.hpp).  The contract: the output equals, bit for bit, the
 EXISTING fp32 call on the widened input under SAVGOL_BATCH_TILE_NARROW, rounded to nearest even into the output type (torch's CPU cast) -- every half
 window, boundary mode, VALID, derivative, type pair and served flag; ragged lengths, odd pitches and shifted bases with guarded NaN-filled outputs;
 Inf / NaN / subnormal / overflowing values; the fp64 oracle within u + (1 + u) x the fp32 bar; refused calls launch nothing; one full-size run; graph

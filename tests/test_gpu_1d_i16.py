@@ -1,4 +1,4 @@
-"""GPU tests of the int16-storage 1-D batch call (savgol_apply[_valid]_batch_i16, sg_k1d_i16.hpp).  The contract: the output equals, bit for bit, the
+"""GPU tests of the int16-storage 1-D batch call (savgol_apply[_valid]_batch_i16, sg_k1d_st16.hpp).  The contract: the output equals, bit for bit, the
 EXISTING fp32 call on the widened input under SAVGOL_BATCH_TILE_NARROW; for int16 output that result rounded to nearest even, saturated to
 [-32768, 32767], NaN -> 0 (torch.round / nan_to_num / clamp / cast on the CPU) -- every half window, boundary mode, VALID, derivative, both output
 types and every served flag; ragged lengths, odd pitches and shifted bases with guarded sentinel-filled outputs; +-Inf / NaN results; derivative

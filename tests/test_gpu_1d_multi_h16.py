@@ -1,4 +1,4 @@
-"""GPU tests of the fused multi-output 1-D call on 16-bit storage (savgol_apply[_valid]_multi_batch_h16, sg_k1d_multi_h16.hpp).  The contract: output k
+"""GPU tests of the fused multi-output 1-D call on 16-bit storage (savgol_apply[_valid]_multi_batch_h16, sg_k1d_multi_st16.hpp).  The contract: output k
 equals, bit for bit, the EXISTING 16-bit single call with SAVGOL_BATCH_PLAIN_SUMMATION, and output k of the EXISTING fp32 fused call on the widened
 input under SAVGOL_BATCH_TILE_NARROW rounded to nearest even into the output type (torch's CPU cast) -- every half window, boundary mode, VALID, both
 input types and both output choices, counts 2 / 3 / 4 in mixes that put a derivative first, two smoothing filters together, only smoothing (no

@@ -1,4 +1,4 @@
-"""GPU tests of the fused multi-output 1-D call on int16 storage (savgol_apply[_valid]_multi_batch_i16, sg_k1d_multi_i16.hpp).  The contract: output k
+"""GPU tests of the fused multi-output 1-D call on int16 storage (savgol_apply[_valid]_multi_batch_i16, sg_k1d_multi_st16.hpp).  The contract: output k
 equals, bit for bit, the EXISTING int16 single call with SAVGOL_BATCH_PLAIN_SUMMATION, and output k of the EXISTING fp32 fused call on the widened
 input under SAVGOL_BATCH_TILE_NARROW, converted once on the CPU (round to nearest even, saturate, NaN -> 0: to_out) -- every half window, boundary
 mode, VALID, both output types, counts 2 / 3 / 4 in mixes that put a derivative first, two smoothing filters together, only smoothing (no centring)
