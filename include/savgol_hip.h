@@ -649,7 +649,7 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter,
  * factors, which are not the additive form, and is staged; not an x-dominant derivative filter,
  * method 0 or 2), cols % 4 == 0 and cols >= 32, every base, stride and pitch keeps quads naturally aligned (16-bit side: 8-byte base, stride and pitch
  * multiples of 4; fp32 output: 16-byte base), rows x out_stride x element size and the twin's rows x cols x 4 are under 0x7fffff00, and neither
- * SAVGOL_HIP_ROLL_TILE nor SAVGOL_HIP_2D_H16_TILES is 0: the same tiles reading 16-bit rows and storing out_type rows (csrc/sg_2d_roll_h16.inc).
+ * SAVGOL_HIP_ROLL_TILE nor SAVGOL_HIP_2D_H16_TILES is 0: the same tiles reading 16-bit rows and storing out_type rows (csrc/sg_2d_roll_st16.inc).
  * STAGED -- every other call runs the twin itself: whole frames (max(1, 2^24 / (rows x stride)) per piece: 64 MiB per side of stream-ordered
  * scratch unless one frame alone is larger) are widened into aligned fp32 scratch, filtered scratch to scratch and the pixels the twin wrote
  * rounded out.  Pieces of whole frames do not change bits.
@@ -689,7 +689,7 @@ int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter,
  * element sizes are the same).  TILES -- the twin launches the rolling kernel's additive tile form (a smoothing filter of order <= 3 on a square window,
  * half windows 1..16; not an x-dominant filter; method 0 or 2), cols % 4 == 0 and cols >= 32, quads are naturally aligned (int16 side: 8-byte base,
  * stride and pitch multiples of 4; fp32 output: 16-byte base), rows x out_stride x element size and the twin's rows x cols x 4 are under 0x7fffff00,
- * and neither SAVGOL_HIP_ROLL_TILE nor SAVGOL_HIP_2D_I16_TILES is 0: sg2d_rolling_i16_kernel (csrc/sg_2d_roll_i16.inc), the same tiles reading int16 rows
+ * and neither SAVGOL_HIP_ROLL_TILE nor SAVGOL_HIP_2D_I16_TILES is 0: sg2d_rolling_i16_kernel (csrc/sg_2d_roll_st16.inc), the same tiles reading int16 rows
  * and storing out_type rows, the storage types fixed when the kernel is compiled.  STAGED -- every other call (the general, two-output,
  * horizontal-first and accumulating tile forms included) runs the twin itself: whole frames in the 16-bit call's pieces are widened into aligned fp32
  * scratch (sg2d_i16_widen_kernel), filtered scratch to scratch, and the pixels the twin wrote converted out (sg2d_i16_convert_kernel).  Pieces of whole

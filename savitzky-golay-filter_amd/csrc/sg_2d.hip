@@ -23,8 +23,7 @@
 #include <vector>
 
 #include "sg_2d.hpp"
-#include "sg_2d_h16.hpp"
-#include "sg_2d_i16.hpp"
+#include "sg_2d_st16.hpp"
 #include "sg_runtime.hpp"
 
 namespace sg {
@@ -452,10 +451,6 @@ static int host_apply(const char *who, const Savgol2DFilter *f, const float *inp
 }
 
 // ---- what the two 2-D batch calls on 2-byte storage share (savgol2d_apply_batch_h16, savgol2d_apply_batch_i16; the entry points are further down) ----
-static const char *const kH16Who2D = "savgol2d_apply_batch_h16";
-static const char *h16_type_name_2d(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
-static const char *const kI16Who2D = "savgol2d_apply_batch_i16";
-
 // The staged route: the twin itself.  Whole frames per piece, widened into aligned fp32 scratch, savgol2d_apply_batch_f32's own path (enqueue_2d)
 // scratch to scratch, and the pixels it wrote rounded out.  Pieces of whole frames do not change bits: the additive tile's re-seed phase is the
 // tile, the strip walk's the frame row (launch_roll_kernel), and every other 2-D kernel computes its outputs independently.
@@ -486,15 +481,52 @@ static int staged16_2d(const char *who, DeviceCtx *ctx, const Savgol2DFilter *f,
     return hip_ok(hipGetLastError(), who) ? 0 : -1;
 }
 
-// The two calls on 2-byte storage (h16, i16) share everything but the check of their types: `form` names the storage in the method text, `tiles_env` is
-// the call's own switch.
+// The two calls on 2-byte storage share one route (apply16_2d, route16_2d below); what they differ in is their host-side description, the 2-D
+// counterpart of the 1-D calls' H16Host / I16Host (sg_api_1d.cpp):
+//   Family         the device-side policy (sg_2d_st16.hpp): element type, job, tile objects, staged kernels
+//   WHO, FORM      the call's name; the storage's name in the method-1 refusal
+//   TILES_ENV      the call's own switch
+//   types_served   the refusal of a type pair (h16) or an output type (i16) the call does not serve; in_type is ignored where the input has one type
+//   fill           how in_type / out_type map onto the job's storage fields
+struct H16Host2D {
+    typedef H16Family2D Family;
+    static constexpr const char *WHO = "savgol2d_apply_batch_h16", *FORM = "16-bit", *TILES_ENV = "SAVGOL_HIP_2D_H16_TILES";
+    static const char *type_name(int t) { return t == SAVGOL_HIP_F32 ? "f32" : t == SAVGOL_HIP_F16 ? "f16" : t == SAVGOL_HIP_BF16 ? "bf16" : "unknown"; }
+    static bool types_served(int in_type, int out_type)
+    {
+        if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
+            sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", WHO, type_name(in_type), type_name(out_type),
+                         in_type, out_type);
+            return false;
+        }
+        return true;
+    }
+    static void fill(Family::Fields &st, int in_type, int out_type)
+    {
+        st.in_bf = in_type == SAVGOL_HIP_BF16 ? 1 : 0; st.out_bf = out_type == SAVGOL_HIP_BF16 ? 1 : 0; st.out_f32 = out_type == SAVGOL_HIP_F32 ? 1 : 0;
+    }
+};
+struct I16Host2D {
+    typedef I16Family2D Family;
+    static constexpr const char *WHO = "savgol2d_apply_batch_i16", *FORM = "int16", *TILES_ENV = "SAVGOL_HIP_2D_I16_TILES";
+    static bool types_served(int, int out_type)
+    {
+        if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
+            sg_set_error("%s: out_type %d is not served: SAVGOL_HIP_I16 (%d) and SAVGOL_HIP_F32 (%d) are", WHO, out_type, SAVGOL_HIP_I16, SAVGOL_HIP_F32);
+            return false;
+        }
+        return true;
+    }
+    static void fill(Family::Fields &st, int, int out_type) { st.out_f32 = out_type == SAVGOL_HIP_F32 ? 1 : 0; }
+};
+
 static bool method_ok_16(const char *who, int method, const char *form)
 {
     if (method == 1) { sg_set_error("%s: method 1 (the dense kernel in the reference's summation order) is not served: the reference has no %s form to be identical to", who, form); return false; }
     if (method < 0 || method > 3) { sg_set_error("%s: method %d is not one of 0, 2, 3", who, method); return false; }
     return true;
 }
-// Everything after a call's own type check: the remaining refusals in the header's order, then the route: -1 = refused (text set), 0 = nothing to do
+// Everything after a call's method and type checks: the remaining refusals in the header's order, then the route: -1 = refused (text set), 0 = nothing to do
 // (no images) or STAGED, 1 = TILES.  Touches no device.  `factors` / `terms`: the filter's separable factors, for the launch that follows.
 static int plan16_2d(const char *who, const char *tiles_env, const Savgol2DFilter *filter, const void *d_in, int rows, int cols, int in_stride, long long in_pitch,
                      const void *d_out, int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
@@ -522,36 +554,67 @@ static int plan16_2d(const char *who, const char *tiles_env, const Savgol2DFilte
     shape.in_base = in0; shape.out_base = out0; shape.out_elem = out_elem;
     shape.method = method;
     shape.x_dominant = sg2d_x_dominant(filter->config.deriv_x, filter->config.deriv_y);
-    shape.additive_tile = *terms > 0 && sg2d_launch_rolling_h16(nx > ny ? nx : ny, *terms, nullptr, factors, filter->scale, 0, nullptr) == 0;
+    shape.additive_tile = *terms > 0 && roll16_fp32_takes_tiles(nx > ny ? nx : ny, *terms, factors, filter->scale);
     shape.roll_tile_switch = roll_tile_env;
     shape.tiles_switch = !tiles_text || atoi(tiles_text) != 0;
     return frame_plan_h16(shape) == FRAME_H16_TILES ? 1 : 0;
 }
 
-static int h16_plan_2d(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, long long in_pitch, const void *d_out,
-                       int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
+// A call's refusals in the header's order (method, type pair, then plan16_2d's), then its route.  Serves the _route exports as it stands.
+template <class H>
+static int route16_2d(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, long long in_pitch, const void *d_out, int out_type,
+                      int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
 {
-    const char *who = kH16Who2D;
-    if (!method_ok_16(who, method, "16-bit")) return -1;
-    if ((in_type != SAVGOL_HIP_F16 && in_type != SAVGOL_HIP_BF16) || (out_type != in_type && out_type != SAVGOL_HIP_F32)) {
-        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who, h16_type_name_2d(in_type),
-                     h16_type_name_2d(out_type), in_type, out_type);
-        return -1;
-    }
-    return plan16_2d(who, "SAVGOL_HIP_2D_H16_TILES", filter, d_in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, boundary, method, factors, terms);
+    if (!method_ok_16(H::WHO, method, H::FORM) || !H::types_served(in_type, out_type)) return -1;
+    return plan16_2d(H::WHO, H::TILES_ENV, filter, d_in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, boundary, method, factors, terms);
 }
 
-// savgol2d_apply_batch_i16: the same, with its own type check (int16 in; int16 or fp32 out)
-static int i16_plan_2d(const Savgol2DFilter *filter, const void *d_in, int rows, int cols, int in_stride, long long in_pitch, const void *d_out, int out_type,
-                       int out_stride, long long out_pitch, size_t images, int boundary, int method, float *factors, int *terms)
+// The call: fp16 / bf16 or int16 frames in, the same type or fp32 out, the fp32 call's arithmetic in between (contract: savgol_hip.h).
+template <class H>
+static int apply16_2d(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, long long in_pitch, void *d_out, int out_type,
+                      int out_stride, long long out_pitch, size_t images, int boundary, int method, hipStream_t st)
 {
-    const char *who = kI16Who2D;
-    if (!method_ok_16(who, method, "int16")) return -1;
-    if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
-        sg_set_error("%s: out_type %d is not served: SAVGOL_HIP_I16 (%d) and SAVGOL_HIP_F32 (%d) are", who, out_type, SAVGOL_HIP_I16, SAVGOL_HIP_F32);
-        return -1;
+    typedef typename H::Family F;
+    const char *who = H::WHO;
+    float factors[SEP_FACTOR_FLOATS];
+    int terms = 0;
+    // the refusals, in the order the header gives, and the route: decided before anything touches the device
+    const int route = route16_2d<H>(filter, d_in, in_type, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, boundary, method, factors, &terms);
+    if (route < 0) return -1;
+    if (images == 0) return 0;
+    DeviceCtx *ctx = ctx_get();                               // both routes: the context binds the thread to the library's device, as in the fp32 call
+    if (!ctx) return -1;
+    const typename F::Elem *in = static_cast<const typename F::Elem *>(d_in);
+    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    if (route == 1) {
+        Job2DSt16<F> job;
+        memset(&job, 0, sizeof(job));
+        job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
+        job.in_pitch = in_pitch; job.out_pitch = out_pitch;
+        job.nx = filter->config.half_window_x; job.ny = filter->config.half_window_y;
+        job.boundary = (boundary == SAVGOL2D_BOUNDARY_VALID || boundary == SAVGOL2D_BOUNDARY_REFLECT) ? boundary : SAVGOL2D_BOUNDARY_CONSTANT;
+        H::fill(job.st, in_type, out_type);
+        // chunks of images as enqueue_frame cuts them for the twin
+        const size_t max_img = ((size_t)1 << 30) / ((size_t)((cols + 63) / 64) * (size_t)(rows + 1)) + 1;
+        int rc = 0;
+        for (size_t i0 = 0; i0 < images && rc == 0; i0 += max_img) {
+            const unsigned ni = (unsigned)(images - i0 < max_img ? images - i0 : max_img);
+            job.in = in + (long long)i0 * in_pitch;
+            job.out = static_cast<unsigned char *>(d_out) + i0 * (size_t)out_pitch * out_elem;
+            rc = sg2d_launch_rolling_st16<F>(job.nx > job.ny ? job.nx : job.ny, terms, &job, factors, filter->scale, ni, st);
+            if (rc == 1 && i0 > 0) rc = -1;                  // cannot happen: the first chunk's answer holds for all
+        }
+        if (rc == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
+        if (rc < 0) return -1;
+        // "not covered": nothing has been enqueued -- the staged route
     }
-    return plan16_2d(who, "SAVGOL_HIP_2D_I16_TILES", filter, d_in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, boundary, method, factors, terms);
+    return staged16_2d(who, ctx, filter, rows, cols, d_out, out_elem, out_pitch, images, boundary, method, st,
+                       [&](size_t i0, float *sin, size_t ni) {
+                           sg2d_st16_widen_frames<F>(in + (long long)i0 * in_pitch, in_type, in_stride, in_pitch, sin, rows, cols, ni, st);
+                       },
+                       [&](const float *sout, void *out, size_t ni, int xlo, int xhi, int ylo, int yhi) {
+                           sg2d_st16_out_frames<F>(sout, out, out_type, out_stride, out_pitch, rows, cols, xlo, xhi, ylo, yhi, ni, st);
+                       });
 }
 
 }  // namespace sg
@@ -618,143 +681,39 @@ int savgol2d_apply_batch_f32(const Savgol2DFilter *filter, const float *d_in, in
                           out_stride, (long long)out_image_pitch, images, (int)boundary, method, static_cast<hipStream_t>(stream));
 }
 
-// ---- the 2-D batch call on 16-bit storage: fp16 / bf16 frames in, the same type or fp32 out, the fp32 call's arithmetic in between ----
-namespace sg {
-
-
-static int h16_staged_2d(DeviceCtx *ctx, const Savgol2DFilter *f, const unsigned short *d_in, bool ibf, int rows, int cols, int in_stride, long long in_pitch,
-                         void *d_out, int out_type, int out_stride, long long out_pitch, size_t images, int boundary, int method, hipStream_t st)
-{
-    return staged16_2d(kH16Who2D, ctx, f, rows, cols, d_out, out_type == SAVGOL_HIP_F32 ? 4 : 2, out_pitch, images, boundary, method, st,
-                       [&](size_t i0, float *sin, size_t ni) { sg2d_h16_widen_frames(d_in + (long long)i0 * in_pitch, in_stride, in_pitch, ibf, sin, rows, cols, ni, st); },
-                       [&](const float *sout, void *out, size_t ni, int xlo, int xhi, int ylo, int yhi) {
-                           sg2d_h16_round_frames(sout, out, out_type, out_stride, out_pitch, rows, cols, xlo, xhi, ylo, yhi, ni, st);
-                       });
-}
-
-static int i16_staged_2d(DeviceCtx *ctx, const Savgol2DFilter *f, const short *d_in, int rows, int cols, int in_stride, long long in_pitch, void *d_out, int out_type,
-                         int out_stride, long long out_pitch, size_t images, int boundary, int method, hipStream_t st)
-{
-    return staged16_2d(kI16Who2D, ctx, f, rows, cols, d_out, out_type == SAVGOL_HIP_F32 ? 4 : 2, out_pitch, images, boundary, method, st,
-                       [&](size_t i0, float *sin, size_t ni) { sg2d_i16_widen_frames(d_in + (long long)i0 * in_pitch, in_stride, in_pitch, sin, rows, cols, ni, st); },
-                       [&](const float *sout, void *out, size_t ni, int xlo, int xhi, int ylo, int yhi) {
-                           sg2d_i16_convert_frames(sout, out, out_type, out_stride, out_pitch, rows, cols, xlo, xhi, ylo, yhi, ni, st);
-                       });
-}
-
-}  // namespace sg
-
-namespace sg {
-
-// The refusals of the 16-bit call in the header's order, then its route: -1 = refused (text set), 0 = nothing to do (no images) or STAGED, 1 = TILES.
-// Touches no device.  `factors` / `terms`: the filter's separable factors, for the launch that follows.
-}  // namespace sg
-
+// ---- the 2-D batch calls on 16-bit storage (contract: savgol_hip.h): apply16_2d / route16_2d above with the call's description.  The int16 call's
+//      input has one type: its in_type is not looked at ----
 int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
                                    const void *d_out, int out_type, int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method)
 {
     float factors[sg::SEP_FACTOR_FLOATS];
     int terms = 0;
-    return sg::h16_plan_2d(filter, d_in, in_type, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride, (long long)out_image_pitch, images,
-                           (int)boundary, method, factors, &terms);
+    return sg::route16_2d<sg::H16Host2D>(filter, d_in, in_type, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride, (long long)out_image_pitch,
+                                         images, (int)boundary, method, factors, &terms);
 }
 
 int savgol2d_apply_batch_h16(const Savgol2DFilter *filter, const void *d_in, int in_type, int rows, int cols, int in_stride, size_t in_image_pitch,
                              void *d_out, int out_type, int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method,
                              void *stream)
 {
-    using namespace sg;
-    const char *who = kH16Who2D;
-    const long long in_pitch = (long long)in_image_pitch, out_pitch = (long long)out_image_pitch;
-    float factors[SEP_FACTOR_FLOATS];
-    int terms = 0;
-    // the refusals, in the order the header gives, and the route: decided before anything touches the device
-    const int route = h16_plan_2d(filter, d_in, in_type, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, factors, &terms);
-    if (route < 0) return -1;
-    if (images == 0) return 0;
-    DeviceCtx *ctx = ctx_get();                               // both routes: the context binds the thread to the library's device, as in the fp32 call
-    if (!ctx) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned short *in = static_cast<const unsigned short *>(d_in);
-    const bool ibf = in_type == SAVGOL_HIP_BF16;
-    const int out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
-    const int nx = filter->config.half_window_x, ny = filter->config.half_window_y, n = nx > ny ? nx : ny;
-    const int bnd = ((int)boundary == SAVGOL2D_BOUNDARY_VALID || (int)boundary == SAVGOL2D_BOUNDARY_REFLECT) ? (int)boundary : SAVGOL2D_BOUNDARY_CONSTANT;
-    if (route == 1) {
-        Job2DH16 job;
-        memset(&job, 0, sizeof(job));
-        job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
-        job.in_pitch = in_pitch; job.out_pitch = out_pitch;
-        job.nx = nx; job.ny = ny; job.boundary = bnd;
-        job.in_bf = ibf ? 1 : 0; job.out_bf = out_type == SAVGOL_HIP_BF16 ? 1 : 0; job.out_f32 = out_type == SAVGOL_HIP_F32 ? 1 : 0;
-        // chunks of images as enqueue_frame cuts them for the twin
-        const size_t max_img = ((size_t)1 << 30) / ((size_t)((cols + 63) / 64) * (size_t)(rows + 1)) + 1;
-        int rc = 0;
-        for (size_t i0 = 0; i0 < images && rc == 0; i0 += max_img) {
-            const unsigned ni = (unsigned)(images - i0 < max_img ? images - i0 : max_img);
-            job.in = in + (long long)i0 * in_pitch;
-            job.out = static_cast<unsigned char *>(d_out) + i0 * (size_t)out_pitch * (size_t)out_elem;
-            rc = sg2d_launch_rolling_h16(n, terms, &job, factors, filter->scale, ni, st);
-            if (rc == 1 && i0 > 0) rc = -1;                  // cannot happen: the first chunk's answer holds for all
-        }
-        if (rc == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
-        if (rc < 0) return -1;
-        // "not covered": nothing has been enqueued -- the staged route
-    }
-    return h16_staged_2d(ctx, filter, in, ibf, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, st);
+    return sg::apply16_2d<sg::H16Host2D>(filter, d_in, in_type, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride, (long long)out_image_pitch,
+                                         images, (int)boundary, method, static_cast<hipStream_t>(stream));
 }
 
-// ---- the 2-D batch call on int16 storage: int16 frames in, int16 or fp32 out, the fp32 call's arithmetic in between (contract: savgol_hip.h) ----
 int savgol2d_apply_batch_i16_route(const Savgol2DFilter *filter, const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch, const void *d_out,
                                    int out_type, int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method)
 {
     float factors[sg::SEP_FACTOR_FLOATS];
     int terms = 0;
-    return sg::i16_plan_2d(filter, d_in, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride, (long long)out_image_pitch, images, (int)boundary,
-                           method, factors, &terms);
+    return sg::route16_2d<sg::I16Host2D>(filter, d_in, SAVGOL_HIP_I16, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride,
+                                         (long long)out_image_pitch, images, (int)boundary, method, factors, &terms);
 }
 
 int savgol2d_apply_batch_i16(const Savgol2DFilter *filter, const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch, void *d_out, int out_type,
                              int out_stride, size_t out_image_pitch, size_t images, Savgol2DBoundary boundary, int method, void *stream)
 {
-    using namespace sg;
-    const char *who = kI16Who2D;
-    const long long in_pitch = (long long)in_image_pitch, out_pitch = (long long)out_image_pitch;
-    float factors[SEP_FACTOR_FLOATS];
-    int terms = 0;
-    // the refusals, in the order the header gives, and the route: decided before anything touches the device
-    const int route = i16_plan_2d(filter, d_in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, factors, &terms);
-    if (route < 0) return -1;
-    if (images == 0) return 0;
-    DeviceCtx *ctx = ctx_get();
-    if (!ctx) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const short *in = reinterpret_cast<const short *>(d_in);
-    const int out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
-    const int nx = filter->config.half_window_x, ny = filter->config.half_window_y, n = nx > ny ? nx : ny;
-    if (route == 1) {
-        Job2DI16 job;
-        memset(&job, 0, sizeof(job));
-        job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
-        job.in_pitch = in_pitch; job.out_pitch = out_pitch;
-        job.nx = nx; job.ny = ny;
-        job.boundary = ((int)boundary == SAVGOL2D_BOUNDARY_VALID || (int)boundary == SAVGOL2D_BOUNDARY_REFLECT) ? (int)boundary : SAVGOL2D_BOUNDARY_CONSTANT;
-        job.out_f32 = out_type == SAVGOL_HIP_F32 ? 1 : 0;
-        // chunks of images as enqueue_frame cuts them for the twin
-        const size_t max_img = ((size_t)1 << 30) / ((size_t)((cols + 63) / 64) * (size_t)(rows + 1)) + 1;
-        int rc = 0;
-        for (size_t i0 = 0; i0 < images && rc == 0; i0 += max_img) {
-            const unsigned ni = (unsigned)(images - i0 < max_img ? images - i0 : max_img);
-            job.in = in + (long long)i0 * in_pitch;
-            job.out = static_cast<unsigned char *>(d_out) + i0 * (size_t)out_pitch * (size_t)out_elem;
-            rc = sg2d_launch_rolling_i16(n, terms, job, factors, filter->scale, ni, st);
-            if (rc == 1 && i0 > 0) rc = -1;                  // cannot happen: the first chunk's answer holds for all
-        }
-        if (rc == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
-        if (rc < 0) return -1;
-        // "not covered": nothing has been enqueued -- the staged route
-    }
-    return i16_staged_2d(ctx, filter, in, rows, cols, in_stride, in_pitch, d_out, out_type, out_stride, out_pitch, images, (int)boundary, method, st);
+    return sg::apply16_2d<sg::I16Host2D>(filter, d_in, SAVGOL_HIP_I16, rows, cols, in_stride, (long long)in_image_pitch, d_out, out_type, out_stride,
+                                         (long long)out_image_pitch, images, (int)boundary, method, static_cast<hipStream_t>(stream));
 }
 
 // ---- device entry points of the derivative frames.  Square windows: a separable frame per output, each through enqueue_frame --

@@ -27,11 +27,8 @@
 #include <utility>
 
 #include "sg_2d.hpp"
-#ifdef SG_ROLL_H16
-#include "sg_2d_h16.hpp"
-#endif
-#ifdef SG_ROLL_I16
-#include "sg_2d_i16.hpp"
+#if defined(SG_ROLL_H16) || defined(SG_ROLL_I16)
+#include "sg_2d_st16.hpp"
 #endif
 #include "sg_h16.hpp"
 #include "sg_i16.hpp"
@@ -157,11 +154,11 @@ __device__ __forceinline__ unsigned long long roll_wave_vote(bool p) { return __
 // dword stores per row for the lanes that hold such a quad.  (The edge strips on the scalar path cost the tile form 13 %:
 // profiles/r04_2d_tile_experiments.txt.)
 //
-// 16-BIT STORAGE (sg_2d_roll_h16.inc, a build of this file of its own): JOB = Job2DH16, TIN = 16-bit words, TOUT = bytes.  Only load_row and store_row know:
+// 16-BIT STORAGE (sg_2d_roll_st16.inc, a build of this file of its own): JOB = Job2DH16, TIN = 16-bit words, TOUT = bytes.  Only load_row and store_row know:
 // a row's quad is one 8-byte load widened exactly, the ring and everything between the two lambdas is the fp32 text below, and the four results are
 // rounded once on their way out.  With JOB = Job2D and float pointers (every fp32 kernel) the text is what it was.
 //
-// INT16 STORAGE (sg_2d_roll_i16.inc, a third build of this file): JOB = Job2DI16, TIN = short, TOUT = short or float -- the storage types are the
+// INT16 STORAGE (sg_2d_roll_st16.inc, a third build of this file): JOB = Job2DI16, TIN = short, TOUT = short or float -- the storage types are the
 // pointers' own, known when the kernel is compiled.  load_row is one 8-byte load and widen4_i16; store_row issues ONE store of TOUT (int16: narrow4_i16
 // and an 8-byte store; fp32: the fp32 text itself, which a float output pointer simply takes).  An int16 frame holds no NaN and no Inf and nothing a
 // smoothing filter makes of it overflows fp32, so the row's finiteness vote and both cold redo paths are compiled out: a finite frame's bits are those
@@ -214,7 +211,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
             return f32x4{nx, fx_b ? nx : (fx_rev ? q.z : q.y), fx_b ? nx : (fx_rev ? q.y : q.z), nw};
         } else if constexpr (H16) {                          // one 8-byte load, widened exactly; the edge strips' remap works on the widened quad
             const u32x2 raw = *reinterpret_cast<const u32x2 *>(row + (EDGE ? qcol : c0));
-            const f32x2 lo = widen2(raw.x, job.in_bf != 0), hi = widen2(raw.y, job.in_bf != 0);
+            const f32x2 lo = widen2(raw.x, job.st.in_bf != 0), hi = widen2(raw.y, job.st.in_bf != 0);
             const f32x4 q = f32x4{lo.x, lo.y, hi.x, hi.y};
             if constexpr (!EDGE) return q;
             const float nx = fx_w ? q.w : q.x, nw = fx_x ? q.x : q.w;
@@ -234,7 +231,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
     const bool whole = !EDGE || (c0 >= xlo && c0 + 4 <= xhi);
     // 16-bit rows: bytes per stored element, wave-uniform (2, or 4 for fp32 output); every offset below counts it where the fp32 text has its 4
     int es = 4;
-    if constexpr (H16) es = job.out_f32 ? 4 : 2;
+    if constexpr (H16) es = job.st.out_f32 ? 4 : 2;
     if constexpr (I16_NARROW) es = 2;                        // int16 rows out: the element size is the type's (fp32 out takes the fp32 text)
     unsigned col_off = (out_lane && whole) ? (unsigned)(c0 * 4) : 0x80000000u;
     if constexpr (H16 || I16_NARROW) col_off = (out_lane && whole) ? (unsigned)(c0 * es) : 0x80000000u;
@@ -529,10 +526,10 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
                 // the other type through the empty descriptor.  16 -> 16 bit: the four results rounded once to nearest even, two dwords, ONE 8-byte
                 // store (lane offset c0 * 2, row part yo * out_stride * 2); 16 bit -> fp32: the fp32 tile's store.
                 const f32x4 v4 = f32x4{r[0].x, r[0].y, r[1].x, r[1].y};
-                const u32x2 pk = u32x2{narrow2(r[0], job.out_bf != 0), narrow2(r[1], job.out_bf != 0)};
+                const u32x2 pk = u32x2{narrow2(r[0], job.st.out_bf != 0), narrow2(r[1], job.st.out_bf != 0)};
                 const int off = (int)(col_off + (unsigned)(yo * job.out_stride * es));
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v4), (keep_row && job.out_f32) ? rsrc[o] : rsrc_none, off, 0, 2 /* nt */);
-                __builtin_amdgcn_raw_buffer_store_b64(pk, (keep_row && !job.out_f32) ? rsrc[o] : rsrc_none, off, 0, 2 /* nt */);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v4), (keep_row && job.st.out_f32) ? rsrc[o] : rsrc_none, off, 0, 2 /* nt */);
+                __builtin_amdgcn_raw_buffer_store_b64(pk, (keep_row && !job.st.out_f32) ? rsrc[o] : rsrc_none, off, 0, 2 /* nt */);
                 if constexpr (PARTIAL) {
                     // VALID's partial quads: four 2-byte (fp32 output: 4-byte) range-checked stores through the row's descriptor over [xlo, xhi) elements
                     const float v[4] = {r[0].x, r[0].y, r[1].x, r[1].y};
@@ -541,8 +538,8 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
                                                                                           keep_row ? (xhi - xlo) * es : 0, 0x00020000);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[j]), job.out_f32 ? prow : rsrc_none, (int)pcol_off[j], 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b16(h[j], job.out_f32 ? rsrc_none : prow, (int)pcol_off[j], 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[j]), job.st.out_f32 ? prow : rsrc_none, (int)pcol_off[j], 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b16(h[j], job.st.out_f32 ? rsrc_none : prow, (int)pcol_off[j], 0, 0);
                     }
                 }
                 return;
@@ -996,13 +993,15 @@ static int dispatch_roll2(int n, int terms, const Job2D &job, const float *f0, f
     else return 1;
 }
 
+#if defined(SG_ROLL_H16) || defined(SG_ROLL_I16)
+// The two 16-bit-storage builds of this file (Makefile, ROLL_ST16_RULE): the additive tile on fp16 / bf16 rows (SG_ROLL_H16) or on int16 rows (SG_ROLL_I16)
+// and its launcher under the name SEP_ROLL_FN, in place of the fp32 entry points.  Everything above is shared text; no fp32 kernel is instantiated in these builds.
 #ifdef SG_ROLL_H16
-// The 16-bit-storage build of this file (Makefile, ROLL_H16_RULE): the additive tile on 16-bit rows and its launcher under the name SEP_ROLL_FN, in
-// place of the fp32 entry points.  Everything above is shared text; no fp32 kernel is instantiated in this build.
-#include "sg_2d_roll_h16.inc"
-#elif defined(SG_ROLL_I16)
-// The int16-storage build (Makefile, ROLL_I16_RULE): the additive tile on int16 rows, the storage types at compile time, under the name SEP_ROLL_FN.
-#include "sg_2d_roll_i16.inc"
+typedef H16Family2D Roll16Family;
+#else
+typedef I16Family2D Roll16Family;
+#endif
+#include "sg_2d_roll_st16.inc"
 #else
 // 0 = launched, 1 = this object does not cover the case (half window outside SEP_ROLL_MIN_N..SEP_ROLL_MAX_N, no
 // definite parity).  Built once per half-window group (Makefile), each under its own name SEP_ROLL_FN.
@@ -1020,7 +1019,7 @@ int SEP_ROLL_FN2(int n, int terms, const Job2D &job, const float *factors0, floa
     return dispatch_roll2<SEP_ROLL_MIN_N, 1>(n, terms, job, factors0, scale0, factors1, scale1, out1, images, cu_count, st);
 }
 
-#endif  // SG_ROLL_H16
+#endif  // SG_ROLL_H16 || SG_ROLL_I16
 
 #ifdef SG_STAMPS2D
 }  // namespace sg

@@ -1,7 +1,8 @@
 """Per-kernel comparison of the gfx950 code in two builds of a library (or two objects):
    python tools/isa_diff.py LIB_A LIB_B > profiles/some_isa_diff.txt
 Whole code objects never compare equal (a symbol follows the source text), so every kernel is disassembled on its own, addresses and branch
-targets are normalised (a kernel that merely moved reads as the same), and each name prints `same` or `differs`; for those that differ the
+targets are normalised (a kernel that merely moved reads as the same; so does one that is no longer, or newly, the last of its code object and lost or
+gained the object's end padding), and each name prints `same` or `differs`; for those that differ the
 VGPRs, SGPRs, LDS bytes, scratch (private segment) bytes and code length of both sides follow."""
 import os, re, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -34,14 +35,19 @@ def kernels(path):
             m = re.match(r"([0-9a-f]{16}) <(.*)>:$", head)
             if not m or m.group(2) not in res:
                 continue
-            start, ins = int(m.group(1), 16), []
+            start, ins, at = int(m.group(1), 16), [], []
             for line in body.split("\n"):
                 # "\ts_cbranch_scc1 65500   // 000000001234: BF85FFDC <name+0x1c>": keep the mnemonic and operands; a branch keeps its target's offset
                 # inside the kernel instead of the encoded distance (which is the same thing, but the encoding column goes)
                 t = re.match(r"\s+(\S+)(.*?)\s*// ([0-9A-F]{12}): [0-9A-F ]+(?:<.*?\+0x([0-9a-f]+)>)?", line)
                 if t:
                     ins.append(t.group(1) + ((" @" + t.group(4)) if t.group(4) and t.group(1).startswith("s_") else t.group(2)))
-            end = int(re.findall(r"// ([0-9A-F]{12}):", body)[-1], 16) if ins else start
+                    at.append(int(t.group(3), 16))
+            # the s_nop run that pads the end of a code object is listed under its LAST kernel: not that kernel's code (no kernel ends in an s_nop it runs),
+            # and which kernel is last changes when two translation units become one
+            while ins and ins[-1].startswith("s_nop"):
+                ins.pop(), at.pop()
+            end = at[-1] if ins else start
             out[re.sub(r"\(.*", "", pretty[m.group(2)])] = (ins, dict(res[m.group(2)], code=end - start + 4))
             found.add(m.group(2))
         assert found == set(res), f"kernels in the metadata that the disassembly does not show: {sorted(set(res) - found)[:3]}"
