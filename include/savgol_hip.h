@@ -702,8 +702,8 @@ int savgol2d_apply_batch_h16_route(const Savgol2DFilter *filter,
  * The twin's own late refusal is kept as the 16-bit call has it: "no separable kernel ..." on the staged route with method 2 or 3 (d_out untouched).
  * images == 0 returns 0.  Like its siblings it only enqueues (after one warm-up call with the same filter), so it can be captured into a graph.
  * Not served: uint16 pixels (12- and 14-bit unsigned data, everything below 32768, can be passed as int16 as it is); a gain or offset per call;
- * int16 -> fp16 / bf16 pairs; the derivative-frame and row-band calls; in place; the general, two-output, horizontal-first and accumulating tile forms
- * on int16 rows (they take the staged route); bench.py (the flagship workload stays fp32).  savgol2d_apply_batch_h16 keeps refusing SAVGOL_HIP_I16. */
+ * int16 -> fp16 / bf16 pairs; the Hessian, Laplacian and row-band calls (the gradient on int16 frames: savgol2d_gradient_batch_i16 below); in place; the
+ * general, two-output, horizontal-first and accumulating tile forms on int16 rows through THIS call (they take the staged route); bench.py (the flagship workload stays fp32).  savgol2d_apply_batch_h16 keeps refusing SAVGOL_HIP_I16. */
 int savgol2d_apply_batch_i16(const Savgol2DFilter *filter,
                              const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
                              void *d_out, int out_type, int out_stride, size_t out_image_pitch,
@@ -714,6 +714,47 @@ int savgol2d_apply_batch_i16_route(const Savgol2DFilter *filter,
                                    const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
                                    const void *d_out, int out_type, int out_stride, size_t out_image_pitch,
                                    size_t images, Savgol2DBoundary boundary, int method);
+
+/* The GRADIENT on INT16 STORAGE: int16 frames in, gx = d/dx and gy = d/dy out as int16 or fp32 frames (out_type: SAVGOL_HIP_I16 or SAVGOL_HIP_F32, both
+ * frames the same type), fp32 arithmetic inside, no fp32 copy of the stack on the caller's side.  Strides and image pitches count elements of their own
+ * buffer; the two outputs share out_stride and out_image_pitch.  Either output pointer may be NULL: that frame is not computed.  With both NULL the call
+ * returns 0 and looks at nothing else, as savgol2d_gradient_batch_f32 does.
+ * CONTRACT (savgol2d_apply_batch_i16's).  The twin is savgol2d_gradient_batch_f32 (declared below) with the same half windows, order, deltas and boundary
+ * on the frames widened exactly to fp32, in buffers with 16-byte aligned bases, stride = cols rounded up to a multiple of 4 and image pitch rows x stride.
+ * An fp32 output pixel is the twin's pixel bit for bit.  An int16 output pixel is the twin's pixel converted ONCE by csrc/sg_i16.hpp's rule: round to
+ * nearest, ties to even; saturate to [-32768, 32767]; NaN -> 0 (reachable only through deltas whose scale overflows).  Pixels the twin does not write are
+ * not written: the VALID border, every byte between cols and the stride and between frames.  None of this depends on the alignment of the caller's buffers.
+ * Two routes, chosen by one host rule before anything is enqueued (csrc/sg_2d_grad16_host.hpp, grad_plan_i16).  DIRECT, for both requested frames, needs all
+ * of: a square window with 1 <= n <= 7; every requested frame's separable factors have one or two terms of definite parity (poly_order <= 4 in practice;
+ * the rule asks the factors), gx's two x factors of one parity; cols % 4 == 0 and cols >= 32; the int16 sides on 8-byte bases with stride and pitch
+ * multiples of 4, an fp32 output on a 16-byte base; rows x out_stride x element size and the twin's rows x cols x 4 under 0x7fffff00 (frame_plan_h16's
+ * layout conditions, asked of frame_plan_h16); neither SAVGOL_HIP_ROLL_TILE nor SAVGOL_HIP_2D_GRAD_I16_DIRECT is 0.  Then the twin itself runs the
+ * horizontal-first kernel for gx and the general 20-row tile for gy, and this call runs the same two on int16 rows: sg2d_rolling_hf_i16_kernel
+ * (csrc/sg_2d_hf.hip) and sg2d_rolling_gen_i16_kernel (csrc/sg_2d_roll_st16.inc), gx first, with the twin's taps and term sums.  STAGED -- every other call
+ * (half windows above 7, rectangular windows, order >= 5, odd layouts) runs the twin itself: whole frames in pieces (three fp32 sides within 128 MiB:
+ * grad_stage_i16) are widened ONCE into aligned fp32 scratch (sg2d_i16_widen_kernel), savgol2d_gradient_batch_f32's own path runs scratch to scratch for
+ * the requested frames, and each is converted out (sg2d_i16_convert_kernel); one stream-ordered allocate / free pair per call.  Pieces of whole frames do
+ * not change bits.  SAVGOL_HIP_2D_GRAD_I16_DIRECT is read with getenv at every call (SAVGOL_HIP_ROLL_TILE once per process); set it before threads start.
+ * Returns -1 with a text naming savgol2d_gradient_batch_i16, before any launch or scratch allocation; the checks run in this order and the first fault wins:
+ *   1. an out_type other than SAVGOL_HIP_I16 / SAVGOL_HIP_F32 (named);   2. a NULL d_in;
+ *   3. the configuration and the geometry savgol2d_gradient_batch_f32 refuses, with its texts (invalid configuration, bad image geometry, image smaller
+ *      than the window);
+ *   4. stacks that share a byte (compared byte-wise: element sizes 2 and 2 or 4): the input against each output, then the two outputs against each other.
+ * images == 0 returns 0 once 1-3 have passed.  Like its siblings it only enqueues (after one warm-up call with the same arguments), so it can be captured
+ * into a graph.
+ * Not served: Hessian and Laplacian on int16; fp16 / bf16 frames; half windows above 7, rectangular windows and order >= 5 on the direct route (they are
+ * staged); accumulating passes with 16-bit outputs; a one-read gradient (each frame reads the input once); mixed output types; uint16 pixels; in place;
+ * bench.py.  The route and bits of savgol2d_apply_batch_i16 are unchanged. */
+int savgol2d_gradient_batch_i16(int half_win_x, int half_win_y, int poly_order,
+                                const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
+                                void *d_grad_x, void *d_grad_y, int out_type, int out_stride, size_t out_image_pitch,
+                                size_t images, float delta_x, float delta_y, Savgol2DBoundary boundary, void *stream);
+/* Which route the call above would take for these arguments, decided by the same code and touching no device: 1 = DIRECT, 0 = STAGED (or nothing to do:
+ * no images, both outputs NULL), -1 = the call would be refused before any launch (same order, same texts). */
+int savgol2d_gradient_batch_i16_route(int half_win_x, int half_win_y, int poly_order,
+                                      const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
+                                      const void *d_grad_x, const void *d_grad_y, int out_type, int out_stride, size_t out_image_pitch,
+                                      size_t images, float delta_x, float delta_y, Savgol2DBoundary boundary);
 
 /* Derivative frames (arithmetic of savgol2d_gradient / _hessian / _laplacian, src/savgol2d.c:462-618).  The Laplacian
  * writes one frame, with no temporary frame and no add pass.  Outputs may be NULL (skipped), like the reference.

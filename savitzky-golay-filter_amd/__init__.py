@@ -183,6 +183,8 @@ SIGNATURES = {
     "savgol2d_apply_batch_h16_route": (C.c_int, [_F2, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int]),
     "savgol2d_apply_batch_i16": (C.c_int, [_F2, _vp, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp]),
     "savgol2d_apply_batch_i16_route": (C.c_int, [_F2, _vp, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int]),
+    "savgol2d_gradient_batch_i16": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, _vp, C.c_int, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int, _vp]),
+    "savgol2d_gradient_batch_i16_route": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, _vp, C.c_int, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int]),
     "savgol2d_gradient_batch_f32": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, _vp, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int, _vp]),
     "savgol2d_hessian_batch_f32": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, _vp, _vp, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int, _vp]),
     "savgol2d_laplacian_batch_f32": (C.c_int, [C.c_int] * 3 + [_vp, C.c_int, C.c_int, C.c_int, _sz, _vp, C.c_int, _sz, _sz, C.c_float, C.c_float, C.c_int, _vp]),
@@ -799,3 +801,32 @@ class Filter2D:
         -1 = the call would be refused (last_error() has the text)"""
         return lib().savgol2d_apply_batch_i16_route(*self._i16_args("apply_batch_i16_route", d_in, d_out, rows, cols, images, out_dtype, in_stride, out_stride,
                                                                     in_pitch, out_pitch, boundary, method))
+
+
+def _gradient_i16_args(who, nx, ny, order, d_in, d_gx, d_gy, rows, cols, images, out_dtype, in_stride, out_stride, in_pitch, out_pitch, delta_x, delta_y, boundary):
+    types = {"i16": SAVGOL_HIP_I16, "f32": SAVGOL_HIP_F32}
+    if out_dtype not in types:
+        raise ValueError(f"{who}: out_dtype {out_dtype!r} (\"i16\" or \"f32\")")
+    in_stride = cols if in_stride is None else in_stride
+    out_stride = cols if out_stride is None else out_stride
+    return (nx, ny, order, _addr(d_in), rows, cols, in_stride, rows * in_stride if in_pitch is None else in_pitch, _addr(d_gx), _addr(d_gy), types[out_dtype], out_stride,
+            rows * out_stride if out_pitch is None else out_pitch, images, delta_x, delta_y, boundary)
+
+
+def gradient_batch_i16(nx, ny, order, d_in, d_gx, d_gy, rows, cols, images, out_dtype="i16", in_stride=None, out_stride=None, in_pitch=None, out_pitch=None,
+                       delta_x=1.0, delta_y=1.0, boundary=SAVGOL2D_BOUNDARY_VALID, stream=None):
+    """savgol2d_gradient_batch_i16: frames of int16 pixels, gx and gy of out_dtype ("i16" or "f32"; either may be None), the fp32 gradient call's arithmetic
+    in between; for "i16" the fp32 call's pixel rounded to nearest even and saturated (NaN gives 0).  Strides and pitches count elements of their own buffer."""
+    args = _gradient_i16_args("gradient_batch_i16", nx, ny, order, d_in, d_gx, d_gy, rows, cols, images, out_dtype, in_stride, out_stride, in_pitch, out_pitch,
+                              delta_x, delta_y, boundary)
+    rc = lib().savgol2d_gradient_batch_i16(*args, _stream(stream))
+    if rc != 0:
+        raise RuntimeError(f"savgol2d_gradient_batch_i16 returned {rc}: {last_error()}")
+
+
+def gradient_batch_i16_route(nx, ny, order, d_in, d_gx, d_gy, rows, cols, images, out_dtype="i16", in_stride=None, out_stride=None, in_pitch=None, out_pitch=None,
+                             delta_x=1.0, delta_y=1.0, boundary=SAVGOL2D_BOUNDARY_VALID):
+    """the route gradient_batch_i16 would take on these arguments, touching no device: 1 = the int16 kernels (direct), 0 = staged through fp32 scratch (or
+    nothing to do), -1 = the call would be refused (last_error() has the text)"""
+    return lib().savgol2d_gradient_batch_i16_route(*_gradient_i16_args("gradient_batch_i16_route", nx, ny, order, d_in, d_gx, d_gy, rows, cols, images, out_dtype,
+                                                                      in_stride, out_stride, in_pitch, out_pitch, delta_x, delta_y, boundary))

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "sg_2d.hpp"
+#include "sg_2d_grad16_host.hpp"
 #include "sg_2d_st16.hpp"
 #include "sg_runtime.hpp"
 
@@ -830,7 +831,196 @@ static int enqueue_derivatives(const char *who, int nx, int ny, int order, const
     return hip_ok(hipGetLastError(), who) ? 0 : -1;
 }
 
+// ---- savgol2d_gradient_batch_i16 (contract: savgol_hip.h): the gradient on int16 frames, the counterpart of apply16_2d above for the fp32 gradient call.
+//      It stands here because its staged route IS enqueue_derivatives.  The route rule is sg_2d_grad16_host.hpp's, asked by the call and by _route alike. ----
+static const char *const GRAD16_WHO = "savgol2d_gradient_batch_i16";
+
+// what the route decision has prepared for the launches that follow: frame 0 = gx (d/dx), 1 = gy (d/dy); a frame that is not requested is left alone
+struct Grad16Frames {
+    bool want[2];
+    Savgol2DConfig cfg[2];
+    float factors[2][SEP_FACTOR_FLOATS];
+    int terms[2];
+};
+
+// The call's refusals in the header's order, then its route: -1 = refused (text set), 0 = nothing to do (no images) or STAGED, 1 = DIRECT.  Touches no device.
+static int plan_grad16(int nx, int ny, int order, const int16_t *d_in, int rows, int cols, int in_stride, long long in_pitch, const void *d_gx, const void *d_gy, int out_type,
+                       int out_stride, long long out_pitch, size_t images, float delta_x, float delta_y, int boundary, Grad16Frames &fr)
+{
+    const char *who = GRAD16_WHO;
+    if (out_type != SAVGOL_HIP_I16 && out_type != SAVGOL_HIP_F32) {
+        sg_set_error("%s: out_type %d is not served: SAVGOL_HIP_I16 (%d) and SAVGOL_HIP_F32 (%d) are", who, out_type, SAVGOL_HIP_I16, SAVGOL_HIP_F32);
+        return -1;
+    }
+    if (!d_in) { sg_set_error("%s: NULL pointer", who); return -1; }
+    // the configuration and geometry texts of the fp32 gradient call (enqueue_derivatives, make_job)
+    if (nx < 0 || nx > 255 || ny < 0 || ny > 255 || order < 0 || order > 255) { sg_set_error("%s: invalid configuration", who); return -1; }
+    const void *outs[2] = {d_gx, d_gy};
+    for (int i = 0; i < 2; ++i) {
+        fr.want[i] = outs[i] != nullptr;
+        fr.terms[i] = 0;
+        memset(&fr.cfg[i], 0, sizeof(fr.cfg[i]));
+        fr.cfg[i].half_window_x = (uint8_t)nx; fr.cfg[i].half_window_y = (uint8_t)ny; fr.cfg[i].poly_order = (uint8_t)order;
+        fr.cfg[i].deriv_x = i == 0 ? 1 : 0; fr.cfg[i].deriv_y = i == 0 ? 0 : 1;
+        fr.cfg[i].delta_x = delta_x; fr.cfg[i].delta_y = delta_y;
+        if (fr.want[i] && !sg2d_config_ok(&fr.cfg[i])) { sg_set_error("%s: invalid configuration", who); return -1; }
+    }
+    if (!geometry_ok(who, nx, ny, rows, cols, in_stride, out_stride, boundary)) return -1;
+    if (images == 0) return 0;
+    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_in), gx0 = reinterpret_cast<uintptr_t>(d_gx), gy0 = reinterpret_cast<uintptr_t>(d_gy);
+    for (int i = 0; i < 2; ++i)
+        if (fr.want[i] && frames_overlap(in0, 2, in_pitch, in_stride, i == 0 ? gx0 : gy0, out_elem, out_pitch, out_stride, rows, cols, images)) {
+            sg_set_error("%s: input and output frames overlap (2-D filtering cannot run in place; compared byte-wise)", who);
+            return -1;
+        }
+    if (fr.want[0] && fr.want[1] && frames_overlap(gx0, out_elem, out_pitch, out_stride, gy0, out_elem, out_pitch, out_stride, rows, cols, images)) {
+        sg_set_error("%s: the two output frames overlap (compared byte-wise)", who);
+        return -1;
+    }
+    // the route.  SAVGOL_HIP_2D_GRAD_I16_DIRECT is read at every call (tools/time_2d_grad_i16.py times both routes interleaved in one process);
+    // SAVGOL_HIP_ROLL_TILE once, as the fp32 launcher reads it
+    const char *const direct_text = getenv("SAVGOL_HIP_2D_GRAD_I16_DIRECT");
+    static const bool roll_tile_env = [] { const char *e = getenv("SAVGOL_HIP_ROLL_TILE"); return !e || atoi(e) != 0; }();
+    GradShapeI16 shape;
+    memset(&shape, 0, sizeof(shape));
+    shape.nx = nx; shape.ny = ny; shape.rows = rows; shape.cols = cols;
+    shape.in_stride = in_stride; shape.in_pitch = in_pitch; shape.out_stride = out_stride; shape.out_pitch = out_pitch;
+    shape.in_base = in0; shape.want_gx = fr.want[0]; shape.want_gy = fr.want[1]; shape.gx_base = gx0; shape.gy_base = gy0;
+    shape.out_elem = (int)out_elem;
+    shape.roll_tile_switch = roll_tile_env;
+    shape.direct_switch = !direct_text || atoi(direct_text) != 0;
+    if (nx == ny && nx >= 1 && nx <= GRAD_I16_DIRECT_MAX_N) {
+        // what the twin's launchers ask of each requested frame's factors: gx -- hf_dispatch's one-launch forms (one term, or two whose x factors share a
+        // parity; every vector of definite parity); gy -- launch_roll's general tile, asked of the launcher itself (nothing is launched)
+        const int n = nx;
+        const size_t tstride = (size_t)2 * (2 * n + 2);
+        for (int i = 0; i < 2; ++i)
+            if (fr.want[i]) fr.terms[i] = sep_factors_cached(&fr.cfg[i], fr.factors[i]);
+        if (fr.want[0] && (fr.terms[0] == 1 || fr.terms[0] == 2)) {
+            bool ok = true;
+            float sx[2] = {0.0f, 0.0f}, sy;
+            for (int t = 0; t < fr.terms[0]; ++t)
+                ok = ok && vector_parity(fr.factors[0] + t * tstride, n, &sx[t]) && vector_parity(fr.factors[0] + t * tstride + (2 * n + 2), n, &sy);
+            shape.gx_direct = ok && (fr.terms[0] == 1 || sx[0] == sx[1]);
+        }
+        if (fr.want[1] && (fr.terms[1] == 1 || fr.terms[1] == 2))
+            shape.gy_direct = sg2d_launch_rolling_gen_i16(n, fr.terms[1], nullptr, fr.factors[1], sg2d_scale(&fr.cfg[1]), 0, nullptr) == 0;
+    }
+    return grad_plan_i16(shape) == GRAD_I16_DIRECT ? 1 : 0;
+}
+
+// STAGED: the twin itself.  Whole frames per piece (grad_stage_i16) widened ONCE, enqueue_derivatives scratch to scratch for the requested frames, each
+// converted out; one stream-ordered allocate / free pair per call.  Pieces of whole frames do not change bits: neither the horizontal-first kernel nor the
+// general tile carries anything from row to row, and every other 2-D kernel computes its outputs independently.
+static int staged_grad16(DeviceCtx *ctx, int nx, int ny, int order, const int16_t *d_in, int rows, int cols, int in_stride, long long in_pitch, void *const (&outs)[2],
+                         int out_type, int out_stride, long long out_pitch, size_t images, float delta_x, float delta_y, int boundary, hipStream_t st)
+{
+    const char *who = GRAD16_WHO;
+    const FrameStageH16 g = grad_stage_i16(rows, cols, images);
+    const size_t side = (g.frames * g.frame * sizeof(float) + 255) & ~(size_t)255;
+    const int nspec = (outs[0] ? 1 : 0) + (outs[1] ? 1 : 0);
+    char *scratch = static_cast<char *>(scratch_alloc(ctx, (size_t)(1 + nspec) * side, st, who));
+    if (!scratch) return -1;
+    float *sin = reinterpret_cast<float *>(scratch);
+    DerivSpec specs[2];
+    void *dst[2];
+    int k = 0;
+    for (int i = 0; i < 2; ++i)
+        if (outs[i]) { specs[k] = DerivSpec{i == 0 ? 1 : 0, i == 0 ? 0 : 1, reinterpret_cast<float *>(scratch + (size_t)(1 + k) * side)}; dst[k] = outs[i]; ++k; }
+    const bool valid = boundary == SAVGOL2D_BOUNDARY_VALID;
+    const int xlo = valid ? nx : 0, xhi = valid ? cols - nx : cols, ylo = valid ? ny : 0, yhi = valid ? rows - ny : rows;
+    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    int rc = 0;
+    for (size_t i0 = 0; i0 < images && rc == 0; i0 += g.frames) {
+        const size_t ni = images - i0 < g.frames ? images - i0 : g.frames;
+        sg2d_st16_widen_frames<I16Family2D>(d_in + (long long)i0 * in_pitch, SAVGOL_HIP_I16, in_stride, in_pitch, sin, rows, cols, ni, st);
+        rc = enqueue_derivatives(who, nx, ny, order, sin, rows, cols, g.stride, g.frame, specs, nspec, false, g.stride, g.frame, ni, delta_x, delta_y, boundary, st);
+        if (rc != 0) break;
+        for (int s = 0; s < nspec; ++s)
+            sg2d_st16_out_frames<I16Family2D>(specs[s].out, static_cast<char *>(dst[s]) + i0 * (size_t)out_pitch * out_elem, out_type, out_stride, out_pitch, rows, cols,
+                                              xlo, xhi, ylo, yhi, ni, st);
+    }
+    const bool freed = scratch_free(scratch, st, who);
+    if (rc != 0 || !freed) return -1;
+    return hip_ok(hipGetLastError(), who) ? 0 : -1;
+}
+
+static int gradient16_2d(int nx, int ny, int order, const int16_t *d_in, int rows, int cols, int in_stride, long long in_pitch, void *d_gx, void *d_gy, int out_type,
+                         int out_stride, long long out_pitch, size_t images, float delta_x, float delta_y, int boundary, hipStream_t st)
+{
+    const char *who = GRAD16_WHO;
+    if (!d_gx && !d_gy) return 0;                            // as the twin: no frame requested, nothing looked at
+    static thread_local Grad16Frames fr;
+    const int route = plan_grad16(nx, ny, order, d_in, rows, cols, in_stride, in_pitch, d_gx, d_gy, out_type, out_stride, out_pitch, images, delta_x, delta_y, boundary, fr);
+    if (route < 0) return -1;
+    if (images == 0) return 0;
+    DeviceCtx *ctx = ctx_get();
+    if (!ctx) return -1;
+    void *const outs[2] = {d_gx, d_gy};
+    const size_t out_elem = out_type == SAVGOL_HIP_F32 ? 4 : 2;
+    bool launched = false;
+    if (route == 1) {
+        // DIRECT: enqueue_derivatives' own preparation -- the factors of sep_factors_cached (plan_grad16), sg2d_scale, the term sums fitted to the frame's
+        // dense table (roll_passes_hf), enqueue_frame's image chunks -- so the taps and sigma are the twin's by construction.  gx first, then gy.
+        const int n = nx;
+        Job2DI16 job;
+        memset(&job, 0, sizeof(job));
+        job.rows = rows; job.cols = cols; job.in_stride = in_stride; job.out_stride = out_stride;
+        job.in_pitch = in_pitch; job.out_pitch = out_pitch;
+        job.nx = nx; job.ny = ny;
+        job.boundary = (boundary == SAVGOL2D_BOUNDARY_VALID || boundary == SAVGOL2D_BOUNDARY_REFLECT) ? boundary : SAVGOL2D_BOUNDARY_CONSTANT;
+        job.st.out_f32 = out_type == SAVGOL_HIP_F32 ? 1 : 0;
+        const size_t tstride = (size_t)2 * (2 * n + 2);
+        float sigma[SEP_MAX_TERMS] = {0.0f, 0.0f, 0.0f, 0.0f};
+        CachedFilter held;
+        if (fr.want[0]) {
+            const Savgol2DFilter *dense = held.get(&fr.cfg[0]);
+            if (!dense) { sg_set_error("%s: weight computation failed", who); return -1; }
+            hf_term_sums(n, fr.terms[0], fr.factors[0], dense, sigma);
+        }
+        const size_t max_img = ((size_t)1 << 30) / ((size_t)((cols + 63) / 64) * (size_t)(rows + 1)) + 1;
+        int rc = 0;
+        for (int i = 0; i < 2 && rc == 0; ++i) {
+            if (!fr.want[i]) continue;
+            const float scale = sg2d_scale(&fr.cfg[i]);
+            for (size_t i0 = 0; i0 < images && rc == 0; i0 += max_img) {
+                const unsigned ni = (unsigned)(images - i0 < max_img ? images - i0 : max_img);
+                job.in = d_in + (long long)i0 * in_pitch;
+                job.out = static_cast<char *>(outs[i]) + i0 * (size_t)out_pitch * out_elem;
+                if (i == 0) rc = sg2d_launch_rolling_hf_i16(n, job, fr.factors[0], scale, sigma[0], fr.terms[0] == 2 ? fr.factors[0] + tstride : nullptr, sigma[1], ni,
+                                                            ctx->cu_count, st);
+                else rc = sg2d_launch_rolling_gen_i16(n, fr.terms[1], &job, fr.factors[1], scale, ni, st);
+                if (rc == 0) launched = true;
+            }
+        }
+        if (rc == 0) return hip_ok(hipGetLastError(), who) ? 0 : -1;
+        if (rc < 0) return -1;
+        // "not covered": before anything has been enqueued it is the staged route's; after a launch it is an error
+        if (launched) { sg_set_error("%s: a kernel of the direct route refused its frame after another had been enqueued", who); return -1; }
+    }
+    return staged_grad16(ctx, nx, ny, order, d_in, rows, cols, in_stride, in_pitch, outs, out_type, out_stride, out_pitch, images, delta_x, delta_y, boundary, st);
+}
+
 }  // namespace sg
+
+int savgol2d_gradient_batch_i16_route(int half_win_x, int half_win_y, int poly_order, const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
+                                      const void *d_grad_x, const void *d_grad_y, int out_type, int out_stride, size_t out_image_pitch, size_t images, float delta_x,
+                                      float delta_y, Savgol2DBoundary boundary)
+{
+    if (!d_grad_x && !d_grad_y) return 0;
+    static thread_local sg::Grad16Frames fr;
+    return sg::plan_grad16(half_win_x, half_win_y, poly_order, d_in, rows, cols, in_stride, (long long)in_image_pitch, d_grad_x, d_grad_y, out_type, out_stride,
+                           (long long)out_image_pitch, images, delta_x, delta_y, (int)boundary, fr);
+}
+
+int savgol2d_gradient_batch_i16(int half_win_x, int half_win_y, int poly_order, const int16_t *d_in, int rows, int cols, int in_stride, size_t in_image_pitch,
+                                void *d_grad_x, void *d_grad_y, int out_type, int out_stride, size_t out_image_pitch, size_t images, float delta_x, float delta_y,
+                                Savgol2DBoundary boundary, void *stream)
+{
+    return sg::gradient16_2d(half_win_x, half_win_y, poly_order, d_in, rows, cols, in_stride, (long long)in_image_pitch, d_grad_x, d_grad_y, out_type, out_stride,
+                             (long long)out_image_pitch, images, delta_x, delta_y, (int)boundary, static_cast<hipStream_t>(stream));
+}
 
 int savgol2d_gradient_batch_f32(int half_win_x, int half_win_y, int poly_order, const float *d_in, int rows, int cols, int in_stride,
                                 size_t in_image_pitch, float *d_grad_x, float *d_grad_y, int out_stride, size_t out_image_pitch,

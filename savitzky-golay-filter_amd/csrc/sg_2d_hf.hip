@@ -19,8 +19,13 @@
 
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "sg_2d.hpp"
+#ifdef SG_HF_I16
+#include "sg_2d_st16.hpp"
+#endif
+#include "sg_i16.hpp"
 #include "sg_pk.hpp"
 #include "sg_runtime.hpp"
 
@@ -48,11 +53,22 @@ struct HfTaps {
 constexpr int HF_TWO_TERMS_MAX_N = 8;               // two rings of h rows: 2 x 4 (2N + 1 + P) registers
 
 // MODE 1: the strip's 256 input columns are inside the frame, all SW output columns are stored, rows 16-byte aligned; 0: remapped scalar loads, masked stores
-template <int N, int MODE, bool ACC, int NT>
-__device__ __forceinline__ void hf_item(const Job2D &job, const HfTaps<N, NT> &taps, float *mine, const float *in, float *out, int xload, int yb, int nout,
+//
+// INT16 STORAGE (the SG_HF_I16 build of this file, savgol2d_gradient_batch_i16's x frame): JOB = Job2DI16, TIN = short, TOUT = short or float -- the storage
+// types are the pointers' own, known when the kernel is compiled, as in roll_item (sg_2d_roll.hip).  Only load_row and store_row know: a row's quad is one
+// 8-byte load and widen4_i16 (MODE 0: four remapped 2-byte loads, each widened exactly), the ring, the centred pass and the vertical pass are the fp32 text
+// below, and store_row issues ONE store of TOUT per row (int16: narrow4_i16 and an 8-byte store, MODE 0 masked 2-byte stores; fp32: the fp32 text itself).
+// An int16 row holds nothing non-finite, so the centre's finiteness guard is compiled out: a finite centre's bits are those of the text with the guard.
+// Every branch on I16 is `if constexpr`: with JOB = Job2D and float pointers (every fp32 kernel) the text is what it was.
+template <int N, int MODE, bool ACC, int NT, class JOB, class TIN, class TOUT>
+__device__ __forceinline__ void hf_item(const JOB &job, const HfTaps<N, NT> &taps, float *mine, const TIN *in, TOUT *out, int xload, int yb, int nout,
                                         int lane, int xlo, int xhi, int ylo, int yhi)
 {
     typedef Hf<N> R;
+    constexpr bool I16 = std::is_same<TIN, short>::value;                    // int16 rows in; TOUT = short or float
+    constexpr bool I16_NARROW = I16 && std::is_same<TOUT, short>::value;     // ... and int16 rows out
+    static_assert(I16 || (std::is_same<TIN, float>::value && std::is_same<TOUT, float>::value), "fp32 rows, or int16 rows in");
+    static_assert(!I16 || (!ACC && (std::is_same<TOUT, short>::value || std::is_same<TOUT, float>::value)), "int16 rows: plain passes, int16 or fp32 out");
     constexpr bool VEC = MODE != 0;
     const int c0 = xload + 4 * lane;
     int ix0 = 0, ix1 = 0, ix2 = 0, ix3 = 0;
@@ -62,8 +78,12 @@ __device__ __forceinline__ void hf_item(const Job2D &job, const HfTaps<N, NT> &t
     }
     const bool reflect = job.boundary == SAVGOL2D_BOUNDARY_REFLECT;
     auto load_row = [&](int r) -> f32x4 {                    // band row r = frame row yb - N + r, remapped at the frame border; rows past the band: clamped re-reads nobody uses
-        const float *row = in + (long long)fix_row(yb - N + r, job.rows, reflect) * job.in_stride;
-        if constexpr (VEC) return *reinterpret_cast<const f32x4 *>(row + c0);
+        const TIN *row = in + (long long)fix_row(yb - N + r, job.rows, reflect) * job.in_stride;
+        if constexpr (I16 && VEC) {                          // one 8-byte load and one exact convert per element
+            const float4 w = widen4_i16(*reinterpret_cast<const u32x2 *>(row + c0));
+            return f32x4{w.x, w.y, w.z, w.w};
+        } else if constexpr (I16) return f32x4{(float)row[ix0], (float)row[ix1], (float)row[ix2], (float)row[ix3]};
+        else if constexpr (VEC) return *reinterpret_cast<const f32x4 *>(row + c0);
         else return f32x4{row[ix0], row[ix1], row[ix2], row[ix3]};
     };
     const bool out_lane = lane >= R::HL && lane < 64 - R::HL;
@@ -87,8 +107,9 @@ __device__ __forceinline__ void hf_item(const Job2D &job, const HfTaps<N, NT> &t
         // (tools/emulate_2d_passes.py --centre): 1.2-2.4e-7 of the output whatever the offset, where the plain pass (and the reference's own loop) grow with it.
         // A non-finite centre counts as 0 (the 1-D kernels' guard): NaN - NaN and Inf - Inf would put a NaN into every tap of the lane's four outputs, the
         // columns whose window does not hold the pixel included.  With c = 0 the specials meet the taps as in the plain pass; a finite c is untouched.
+        // (int16 rows: every sample is finite -- the guard is not compiled)
         float c = win[s].x;
-        if (!(c - c == 0.0f)) c = 0.0f;
+        if constexpr (!I16) { if (!(c - c == 0.0f)) c = 0.0f; }
         const f32x2 cc = f32x2{c, c};
         f32x2 e[2 * R::NQ + 1];
 #pragma unroll
@@ -173,7 +194,7 @@ __device__ __forceinline__ void hf_item(const Job2D &job, const HfTaps<N, NT> &t
     };
     f32x4 prevq[R::PR];
     auto load_prev = [&](int yo) -> f32x4 {                  // ACC: what the output frame holds in this lane's columns of frame row yo
-        const float *orow = out + (long long)(yo < job.rows ? yo : job.rows - 1) * job.out_stride;
+        const TOUT *orow = out + (long long)(yo < job.rows ? yo : job.rows - 1) * job.out_stride;
         if constexpr (VEC) return *reinterpret_cast<const f32x4 *>(orow + c0);
         else {
             const bool row_ok = yo >= ylo && yo < yhi;
@@ -183,8 +204,20 @@ __device__ __forceinline__ void hf_item(const Job2D &job, const HfTaps<N, NT> &t
     };
     auto store_row = [&](const f32x4 r, int yo) {
         if (yo >= ylo && yo < yhi && yo < yend) {            // uniform
-            float *orow = out + (long long)yo * job.out_stride;
-            if constexpr (VEC) {
+            TOUT *orow = out + (long long)yo * job.out_stride;
+            if constexpr (I16_NARROW) {
+                // int16 rows out: the four results converted once (round to nearest even, saturate, NaN -> 0), two dwords, ONE 8-byte store; the edge
+                // strips store the same four halves one by one under the column mask
+                const u32x2 pk = narrow4_i16(float4{r.x, r.y, r.z, r.w});
+                if constexpr (VEC) {
+                    if (out_lane) __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(orow + c0));
+                } else if (out_lane) {
+                    if (c0 >= xlo && c0 < xhi) orow[c0] = (short)(pk.x & 0xffffu);
+                    if (c0 + 1 >= xlo && c0 + 1 < xhi) orow[c0 + 1] = (short)(pk.x >> 16);
+                    if (c0 + 2 >= xlo && c0 + 2 < xhi) orow[c0 + 2] = (short)(pk.y & 0xffffu);
+                    if (c0 + 3 >= xlo && c0 + 3 < xhi) orow[c0 + 3] = (short)(pk.y >> 16);
+                }
+            } else if constexpr (VEC) {
                 if (out_lane) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, r), reinterpret_cast<u32x4 *>(orow + c0));
             } else if (out_lane) {
                 if (c0 >= xlo && c0 < xhi) orow[c0] = r.x;
@@ -226,31 +259,24 @@ template <int N, bool ACC, int NT>
 __global__ __launch_bounds__(64 * Hf<N>::WPB, NT == 2 ? 1 : hf_min_waves(N)) void sg2d_rolling_hf_kernel(const Job2D job, const HfTaps<N, NT> taps, unsigned strips, unsigned bands,
                                                                                               int band_rows, unsigned total_items, int aligned)
 {
-    typedef Hf<N> R;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *mine = lds + wv * R::BUFW;
-    // blocks that share an XCD (blockIdx % 8, observed placement; speed only) take neighbouring items
-    const unsigned nblk = gridDim.x;
-    const unsigned blk = (blockIdx.x & 7u) * (nblk >> 3) + (blockIdx.x >> 3);
-    const unsigned item = blk * R::WPB + (unsigned)wv;
-    if (item >= total_items) return;
-    const bool valid = job.boundary == SAVGOL2D_BOUNDARY_VALID;
-    const int xlo = valid ? job.nx : 0, xhi = valid ? job.cols - job.nx : job.cols;
-    const int ylo = valid ? job.ny : 0, yhi = valid ? job.rows - job.ny : job.rows;
-    const unsigned strip = item % strips, ib = item / strips;
-    const unsigned band = ib % bands, img = ib / bands;
-    const int yb = (int)band * band_rows;
-    const int nout = job.rows - yb < band_rows ? job.rows - yb : band_rows;
-    const float *in = job.in + (long long)img * job.in_pitch;
-    float *out = job.out + (long long)img * job.out_pitch;
-    const int sx = (int)strip * R::SW;
-    if (aligned == 3 && sx - 4 * R::HL >= 0 && sx - 4 * R::HL + 256 <= job.cols && sx >= xlo && sx + R::SW <= xhi)
-        hf_item<N, 1, ACC, NT>(job, taps, mine, in, out, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);
-    else
-        hf_item<N, 0, ACC, NT>(job, taps, mine, in, out, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);
+    typedef float TIN;
+    typedef float TOUT;
+#include "sg_2d_hf_body.inc"
 }
+
+#ifdef SG_HF_I16
+// The same item on int16 rows (hf_item with TIN = short): one and two terms, never accumulating; OUT_F32 picks the rows stored.  The fp32 kernel's launch
+// bounds, strips, bands, block order and LDS row.  7 half windows x 2 term counts x 2 output types = 28 kernels, built in objects of their own (Makefile).
+template <int N, int NT, bool OUT_F32>
+__global__ __launch_bounds__(64 * Hf<N>::WPB, NT == 2 ? 1 : hf_min_waves(N)) void sg2d_rolling_hf_i16_kernel(const Job2DI16 job, const HfTaps<N, NT> taps, unsigned strips,
+                                                                                                  unsigned bands, int band_rows, unsigned total_items, int aligned)
+{
+    typedef short TIN;
+    typedef typename std::conditional<OUT_F32, float, short>::type TOUT;
+    constexpr bool ACC = false;
+#include "sg_2d_hf_body.inc"
+}
+#endif
 
 // ---- host ----
 // term t of the launch's taps; false: no definite parity, or (t = 1) an x parity other than term 0's
@@ -273,18 +299,18 @@ static bool hf_fill_taps(HfTaps<N, NT> &taps, int t, const float *factors, float
     return true;
 }
 
-template <int N, bool ACC, int NT>
-static int hf_launch(const Job2D &job, const HfTaps<N, NT> &taps, unsigned images, int cu_count, hipStream_t st)
+// The launch geometry of one kernel instance: strips, the band count chosen for whole rounds of the resident waves, launches split over images.  KERNEL: the
+// instance (a template argument: its resident blocks per CU are asked once per instance); `aligned`: bit 0 / 1 = the input's / output's quads are naturally aligned (what MODE 1 needs); advance(part, i0): the job of the launch that
+// starts at frame i0.
+template <int N, int NT, auto KERNEL, class JOB, class ADVANCE>
+static int hf_launch_kernel(const JOB &job, const HfTaps<N, NT> &taps, int aligned, unsigned images, int cu_count, hipStream_t st, ADVANCE advance)
 {
     typedef Hf<N> R;
-    int aligned = 0;
-    if (job.in_stride % 4 == 0 && job.in_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.in) & 15u) == 0) aligned |= 1;
-    if (job.out_stride % 4 == 0 && job.out_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.out) & 15u) == 0) aligned |= 2;
     const unsigned strips = (unsigned)((job.cols + R::SW - 1) / R::SW);
     const size_t lds = sizeof(float) * R::WPB * R::BUFW;
     static const int per_cu = [&] {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sg2d_rolling_hf_kernel<N, ACC, NT>, 64 * R::WPB, lds) != hipSuccess || nb < 1) nb = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL, 64 * R::WPB, lds) != hipSuccess || nb < 1) nb = 1;
         return nb > 4 ? 4 : nb;
     }();
     const unsigned nwaves = (unsigned)cu_count * (unsigned)per_cu * R::WPB;
@@ -307,14 +333,75 @@ static int hf_launch(const Job2D &job, const HfTaps<N, NT> &taps, unsigned image
         const unsigned long long total = ni * per_image;
         unsigned grid = (unsigned)((total + R::WPB - 1) / R::WPB);
         grid = (grid + 7u) & ~7u;
-        Job2D part = job;
-        part.in = job.in + (long long)i0 * job.in_pitch;
-        part.out = job.out + (long long)i0 * job.out_pitch;
-        hipLaunchKernelGGL((sg2d_rolling_hf_kernel<N, ACC, NT>), dim3(grid), dim3(64 * R::WPB), lds, st, part, taps, strips, bands, band_rows, (unsigned)total, aligned);
+        JOB part = job;
+        advance(part, i0);
+        hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(64 * R::WPB), lds, st, part, taps, strips, bands, band_rows, (unsigned)total, aligned);
     }
     return 0;
 }
 
+#ifndef SG_HF_I16
+template <int N, bool ACC, int NT>
+static int hf_launch(const Job2D &job, const HfTaps<N, NT> &taps, unsigned images, int cu_count, hipStream_t st)
+{
+    int aligned = 0;
+    if (job.in_stride % 4 == 0 && job.in_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.in) & 15u) == 0) aligned |= 1;
+    if (job.out_stride % 4 == 0 && job.out_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.out) & 15u) == 0) aligned |= 2;
+    return hf_launch_kernel<N, NT, &sg2d_rolling_hf_kernel<N, ACC, NT>>(job, taps, aligned, images, cu_count, st, [&](Job2D &part, unsigned long long i0) {
+        part.in = job.in + (long long)i0 * job.in_pitch;
+        part.out = job.out + (long long)i0 * job.out_pitch;
+    });
+}
+#else
+// int16 rows: a quad of the input is 8 bytes, a quad of the output 8 (int16) or 16 (fp32)
+template <int N, int NT, bool OUT_F32>
+static int hf_launch_i16(const Job2DI16 &job, const HfTaps<N, NT> &taps, unsigned images, int cu_count, hipStream_t st)
+{
+    int aligned = 0;
+    if (job.in_stride % 4 == 0 && job.in_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.in) & 7u) == 0) aligned |= 1;
+    if (job.out_stride % 4 == 0 && job.out_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(job.out) & (OUT_F32 ? 15u : 7u)) == 0) aligned |= 2;
+    // The only caller is the DIRECT route, whose rule (frame_plan_h16's layout conditions) admits naturally aligned frames alone: a launch that would run
+    // every strip in MODE 0 is not this launcher's to make.  "Not covered": nothing has been enqueued, the caller takes the staged route.  (MODE 0 stays
+    // in the kernel for the strips at the frame's left and right edge.)
+    if (aligned != 3) return 1;
+    return hf_launch_kernel<N, NT, &sg2d_rolling_hf_i16_kernel<N, NT, OUT_F32>>(job, taps, aligned, images, cu_count, st, [&](Job2DI16 &part, unsigned long long i0) {
+        part.in = job.in + (long long)i0 * job.in_pitch;
+        part.out = static_cast<char *>(job.out) + (size_t)i0 * (size_t)job.out_pitch * (OUT_F32 ? 4 : 2);
+    });
+}
+
+template <int N>
+static int hf_dispatch_i16(int n, const Job2DI16 &job, const float *factors, float scale, float sigma, const float *factors2, float sigma2, unsigned images, int cu_count,
+                           hipStream_t st)
+{
+    if (n == N) {
+        static_assert(N <= HF_TWO_TERMS_MAX_N, "the two-term launch");
+        if (factors2) {
+            HfTaps<N, 2> taps;
+            memset(&taps, 0, sizeof(taps));
+            if (!hf_fill_taps<N, 2>(taps, 0, factors, scale, sigma) || !hf_fill_taps<N, 2>(taps, 1, factors2, scale, sigma2)) return 1;
+            return job.st.out_f32 ? hf_launch_i16<N, 2, true>(job, taps, images, cu_count, st) : hf_launch_i16<N, 2, false>(job, taps, images, cu_count, st);
+        }
+        HfTaps<N, 1> taps;
+        memset(&taps, 0, sizeof(taps));
+        if (!hf_fill_taps<N, 1>(taps, 0, factors, scale, sigma)) return 1;
+        return job.st.out_f32 ? hf_launch_i16<N, 1, true>(job, taps, images, cu_count, st) : hf_launch_i16<N, 1, false>(job, taps, images, cu_count, st);
+    }
+    if constexpr (N < SG_HF_MAX_N) return hf_dispatch_i16<N + 1>(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st);
+    else return 1;
+}
+
+// The fp32 entry point's contract on int16 rows (sg_2d_grad16_host.hpp's DIRECT route): ONE launch of one term, or of two whose x factors share a parity;
+// the taps are filled by the fp32 launcher's own hf_fill_taps.  0 = launched, 1 = not covered (nothing has been enqueued), -1 = error.
+int SG_HF_FN(int n, const Job2DI16 &job, const float *factors, float scale, float sigma, const float *factors2, float sigma2, unsigned images, int cu_count,
+             hipStream_t st)
+{
+    if (n < SG_HF_MIN_N || n > SG_HF_MAX_N) return 1;
+    return hf_dispatch_i16<SG_HF_MIN_N>(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st);
+}
+#endif
+
+#ifndef SG_HF_I16
 template <int N>
 static int hf_dispatch(int n, const Job2D &job, const float *factors, float scale, float sigma, const float *factors2, float sigma2, unsigned images, int cu_count,
                        hipStream_t st)
@@ -348,5 +435,6 @@ int SG_HF_FN(int n, const Job2D &job, const float *factors, float scale, float s
     if (n < SG_HF_MIN_N || n > SG_HF_MAX_N) return 1;
     return hf_dispatch<SG_HF_MIN_N>(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st);
 }
+#endif  // !SG_HF_I16
 
 }  // namespace sg

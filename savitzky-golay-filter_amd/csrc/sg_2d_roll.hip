@@ -27,7 +27,7 @@
 #include <utility>
 
 #include "sg_2d.hpp"
-#if defined(SG_ROLL_H16) || defined(SG_ROLL_I16)
+#if defined(SG_ROLL_H16) || defined(SG_ROLL_I16) || defined(SG_ROLL_I16_GEN)
 #include "sg_2d_st16.hpp"
 #endif
 #include "sg_h16.hpp"
@@ -163,6 +163,8 @@ __device__ __forceinline__ unsigned long long roll_wave_vote(bool p) { return __
 // and an 8-byte store; fp32: the fp32 text itself, which a float output pointer simply takes).  An int16 frame holds no NaN and no Inf and nothing a
 // smoothing filter makes of it overflows fp32, so the row's finiteness vote and both cold redo paths are compiled out: a finite frame's bits are those
 // of the text without the test.  Every branch on I16 below is `if constexpr`: the fp32 and the fp16 / bf16 kernels compile to what they were.
+// The GENERAL one- and two-term tile (BOX = false, NOUT = 1: what the y frame of a gradient runs) takes int16 rows through the same two lambdas and
+// nothing else: it has no vote to drop (savgol2d_gradient_batch_i16; sg2d_rolling_gen_i16_kernel in sg_2d_roll_st16.inc, the SG_ROLL_I16_GEN build).
 template <int N, int NT, int NOUT, int MODE, bool BOX, bool ACC, int TR = 0, class JOB, class TIN, class TOUT>
 __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, NOUT> &taps, float *mine, const TIN *in, TOUT *const (&outs)[NOUT],
                                           int xload, int yb, int nout, int lane, int xlo, int xhi, int ylo, int yhi)
@@ -172,7 +174,7 @@ __device__ __forceinline__ void roll_item(const JOB &job, const RollTaps<N, NT, 
     constexpr bool I16_NARROW = I16 && std::is_same<TOUT, short>::value;     // ... and int16 rows out
     constexpr bool H16 = !std::is_same<TIN, float>::value && !I16;
     static_assert(!H16 || (MODE != 0 && TR > 0 && NOUT == 1), "16-bit rows: tile form on vector loads only");
-    static_assert(!I16 || (MODE != 0 && TR > 0 && NOUT == 1 && BOX), "int16 rows: the additive tile form on vector loads only");
+    static_assert(!I16 || (MODE != 0 && TR > 0 && NOUT == 1 && !ACC && (BOX || NT <= 2)), "int16 rows: the additive and the one- and two-term general tile form on vector loads only");
     static_assert(!I16 || std::is_same<TOUT, short>::value || std::is_same<TOUT, float>::value, "int16 rows: int16 or fp32 out");
     static_assert(!BOX || (NT == 2 && NOUT == 1), "the additive form is one output of two terms");
     static_assert(TR == 0 || !ACC, "tiles are plain passes");
@@ -993,9 +995,10 @@ static int dispatch_roll2(int n, int terms, const Job2D &job, const float *f0, f
     else return 1;
 }
 
-#if defined(SG_ROLL_H16) || defined(SG_ROLL_I16)
-// The two 16-bit-storage builds of this file (Makefile, ROLL_ST16_RULE): the additive tile on fp16 / bf16 rows (SG_ROLL_H16) or on int16 rows (SG_ROLL_I16)
-// and its launcher under the name SEP_ROLL_FN, in place of the fp32 entry points.  Everything above is shared text; no fp32 kernel is instantiated in these builds.
+#if defined(SG_ROLL_H16) || defined(SG_ROLL_I16) || defined(SG_ROLL_I16_GEN)
+// The 16-bit-storage builds of this file (Makefile, ROLL_ST16_RULE): the additive tile on fp16 / bf16 rows (SG_ROLL_H16) or on int16 rows (SG_ROLL_I16), or the
+// general one- and two-term tile on int16 rows (SG_ROLL_I16_GEN, ROLL_GEN16_RULE), and its launcher under the name SEP_ROLL_FN, in place of the fp32 entry
+// points.  Everything above is shared text; no fp32 kernel is instantiated in these builds.
 #ifdef SG_ROLL_H16
 typedef H16Family2D Roll16Family;
 #else
@@ -1019,7 +1022,7 @@ int SEP_ROLL_FN2(int n, int terms, const Job2D &job, const float *factors0, floa
     return dispatch_roll2<SEP_ROLL_MIN_N, 1>(n, terms, job, factors0, scale0, factors1, scale1, out1, images, cu_count, st);
 }
 
-#endif  // SG_ROLL_H16 || SG_ROLL_I16
+#endif  // SG_ROLL_H16 || SG_ROLL_I16 || SG_ROLL_I16_GEN
 
 #ifdef SG_STAMPS2D
 }  // namespace sg

@@ -28,6 +28,8 @@ __global__ __launch_bounds__(64 * roll_wpb(N, TR), roll_st16_waves<H16Family2D>(
 {
     typedef H16Family2D F;
     typedef unsigned char TOUT;
+    constexpr int NT = 2;
+    constexpr bool BOX = true;
 #include "sg_2d_roll_st16_tile.inc"
 }
 template <int N, int TR, bool OUT_F32>
@@ -36,8 +38,31 @@ __global__ __launch_bounds__(64 * roll_wpb(N, TR), roll_st16_waves<I16Family2D>(
 {
     typedef I16Family2D F;
     typedef typename std::conditional<OUT_F32, float, short>::type TOUT;
+    constexpr int NT = 2;
+    constexpr bool BOX = true;
 #include "sg_2d_roll_st16_tile.inc"
 }
+#ifdef SG_ROLL_I16_GEN
+// The GENERAL one- and two-term tile on int16 rows (the y frame of savgol2d_gradient_batch_i16): sg2d_rolling_kernel<N, NT, 1, false, false, 20> with int16
+// rows at one or both ends -- roll_item<N, NT, 1, MODE, false, false, 20> entered with TIN = short, at the fp32 form's waves per SIMD (roll_tile_waves(n, nt,
+// false): three, two for two terms from n = 6) except the one-term tile at n = 7, which is built for two: at three it spills (168 registers + 4 spilled with
+// int16 rows out, + 2 with fp32 rows out: 20 / 12 bytes of scratch); occupancy changes, the tile, the strip width and the bits do not.  7 half windows x 2
+// term counts x 2 output types = 28 kernels, in objects of their own (Makefile, ROLL_GEN16_RULE).  The name matches neither the additive tiles' nor the
+// staged kernels'.
+constexpr int ROLL_GEN16_MAX_N = 7;
+constexpr int roll_gen16_waves(int n, int nt) { return (n == 7 && nt == 1) ? 2 : roll_tile_waves(n, nt, false); }
+template <int N, int NT, bool OUT_F32>
+__global__ __launch_bounds__(64 * roll_wpb(N, ROLL_TILE_ROWS), roll_gen16_waves(N, NT)) void sg2d_rolling_gen_i16_kernel(const Job2DI16 job, const RollTaps<N, NT, 1> taps,
+                                                                                                                   unsigned strips, unsigned bands, unsigned total_items, int aligned)
+{
+    typedef I16Family2D F;
+    typedef typename std::conditional<OUT_F32, float, short>::type TOUT;
+    constexpr int TR = roll_tile_rows(N, NT, 1, false);
+    constexpr bool BOX = false;
+    static_assert(TR == ROLL_TILE_ROWS && N <= ROLL_GEN16_MAX_N, "the general form's 20-row tile");
+#include "sg_2d_roll_st16_tile.inc"
+}
+#endif
 // a family's kernel for one half window (OUT_F32: which of the int16 family's two); a further family names its kernel here
 template <class F, int N, int TR, bool OUT_F32>
 constexpr auto roll_st16_kernel()
@@ -49,13 +74,14 @@ constexpr auto roll_st16_kernel()
 
 // launch_roll_kernel's tile geometry (TR > 0): TR rows per band whatever the batch, whole frames per launch, the XCD chunk of whole frames with at
 // least 128 bands of every strip.  The caller has checked what launch_roll_kernel checks before it takes tiles (frame_plan_h16).
-template <int N, int TR, class F, bool OUT_F32>
-static int launch_roll_st16_kernel(const Job2DSt16<F> &job, const RollTaps<N, 2, 1> &taps, unsigned images, hipStream_t st)
+// (kernel: the instance to launch -- an additive tile of roll_st16_kernel, or a general tile on int16 rows)
+template <int N, int TR, class F, bool OUT_F32, int NT, class KERNEL>
+static int launch_roll_st16_kernel(KERNEL kernel, const Job2DSt16<F> &job, const RollTaps<N, NT, 1> &taps, unsigned images, hipStream_t st)
 {
     typedef Roll<N> R;
     const unsigned strips = (unsigned)((job.cols + R::SW - 1) / R::SW);
     constexpr unsigned WPB = (unsigned)roll_wpb(N, TR);
-    const size_t lds = sizeof(float) * WPB * 2 * 2 * R::BUFW;
+    const size_t lds = sizeof(float) * WPB * 2 * NT * R::BUFW;
     const unsigned bands = (unsigned)((job.rows + TR - 1) / TR);
     const unsigned long long per_image = (unsigned long long)strips * bands;
     const unsigned long long max_items = ((1ull << 32) - 4096) / 64;           // a launch indexes < 2^32 threads: split over images
@@ -75,7 +101,7 @@ static int launch_roll_st16_kernel(const Job2DSt16<F> &job, const RollTaps<N, 2,
         const int chunk_bands = (int)(bands * ((128u + bands - 1u) / bands));
         const unsigned long long chunk_items = (unsigned long long)chunk_bands * strips;
         if (chunk_items % WPB == 0 && chunk_items / WPB < (1u << 22) && chunk_items / WPB * 8u <= grid) aligned_launch |= (int)((unsigned)(chunk_items / WPB) << 8);
-        hipLaunchKernelGGL((roll_st16_kernel<F, N, TR, OUT_F32>()), dim3(grid), dim3(64 * WPB), lds, st, part, taps, strips, bands, (unsigned)total, aligned_launch);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * WPB), lds, st, part, taps, strips, bands, (unsigned)total, aligned_launch);
     }
     return 0;
 }
@@ -91,17 +117,52 @@ static int dispatch_roll_st16(int n, const Job2DSt16<F> *job, const float *facto
             memset(&box, 0, sizeof(box));
             if (!fill_box_taps<N>(box, factors, scale) || !roll_tiles_on()) return 1;
             if (!job) return 0;
-            if constexpr (F::TYPED_OUT) { if (job->st.out_f32) return launch_roll_st16_kernel<N, TR, F, true>(*job, box, images, st); }
-            return launch_roll_st16_kernel<N, TR, F, false>(*job, box, images, st);
+            if constexpr (F::TYPED_OUT) { if (job->st.out_f32) return launch_roll_st16_kernel<N, TR, F, true>(roll_st16_kernel<F, N, TR, true>(), *job, box, images, st); }
+            return launch_roll_st16_kernel<N, TR, F, false>(roll_st16_kernel<F, N, TR, false>(), *job, box, images, st);
         } else return 1;
     }
     if constexpr (N < SEP_ROLL_MAX_N) return dispatch_roll_st16<N + 1>(n, job, factors, scale, images, st);
     else return 1;
 }
 
+#ifdef SG_ROLL_I16_GEN
+// The fp32 launcher's own decisions for one output frame of `terms` terms (launch_roll): two terms that fill_box_taps accepts are the additive form's, not
+// this tile's; the taps are fill_taps' (RollTaps<N, NT, 1>); tiles must be on.  job == NULL: the answer alone, nothing launched.  The caller has checked what launch_roll_kernel checks before it takes tiles.
+template <int N, int NT>
+static int dispatch_roll_gen16(int n, int terms, const Job2DI16 *job, const float *factors, float scale, unsigned images, hipStream_t st)
+{
+    if (n == N && terms == NT) {
+        constexpr int TR = roll_tile_rows(N, NT, 1, false);
+        if (!roll_tiles_on()) return 1;
+        if constexpr (NT == 2) {
+            RollTaps<N, 2, 1> box;
+            memset(&box, 0, sizeof(box));
+            if (fill_box_taps<N>(box, factors, scale)) return 1;
+        }
+        RollTaps<N, NT, 1> taps;
+        memset(&taps, 0, sizeof(taps));
+        if (!fill_taps<N, NT, 1>(taps, 0, factors, scale)) return 1;
+        if (!job) return 0;
+        if (job->st.out_f32) return launch_roll_st16_kernel<N, TR, I16Family2D, true>(&sg2d_rolling_gen_i16_kernel<N, NT, true>, *job, taps, images, st);
+        return launch_roll_st16_kernel<N, TR, I16Family2D, false>(&sg2d_rolling_gen_i16_kernel<N, NT, false>, *job, taps, images, st);
+    }
+    if constexpr (NT < 2) return dispatch_roll_gen16<N, NT + 1>(n, terms, job, factors, scale, images, st);
+    else if constexpr (N < SEP_ROLL_MAX_N) return dispatch_roll_gen16<N + 1, 1>(n, terms, job, factors, scale, images, st);
+    else return 1;
+}
+
+// see sg_2d_st16.hpp (RollGen16Launch)
+int SEP_ROLL_FN(int n, int terms, const Job2DI16 *job, const float *factors, float scale, unsigned images, hipStream_t st)
+{
+    static_assert(SEP_ROLL_MAX_N <= ROLL_GEN16_MAX_N, "built for the half windows whose general form is a 20-row tile");
+    if (n < SEP_ROLL_MIN_N || n > SEP_ROLL_MAX_N || terms < 1 || terms > 2) return 1;
+    return dispatch_roll_gen16<SEP_ROLL_MIN_N, 1>(n, terms, job, factors, scale, images, st);
+}
+#else
 // see sg_2d_st16.hpp
 int SEP_ROLL_FN(int n, int terms, const Job2DSt16<Roll16Family> *job, const float *factors, float scale, unsigned images, hipStream_t st)
 {
     if (n < SEP_ROLL_MIN_N || n > SEP_ROLL_MAX_N || terms != 2) return 1;
     return dispatch_roll_st16<SEP_ROLL_MIN_N>(n, job, factors, scale, images, st);
 }
+#endif

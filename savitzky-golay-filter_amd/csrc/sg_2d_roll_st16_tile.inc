@@ -4,13 +4,14 @@
 // __device__ __forceinline__ function over the family the kernels came out with other registers (job and taps by reference) or, the int16 ones, with the
 // operands of the stores' row-offset multiply commuted (by value); included, every kernel compiles the tokens it always did
 // (profiles/2d_st16_isa_diff.txt).  The including scope provides
-//   constexpr int N, TR;  the family F (sg_2d_st16.hpp) and TOUT, what roll_item stores through (h16: bytes; i16: short or float);
+//   constexpr int N, TR, NT; constexpr bool BOX (the additive form: NT = 2, BOX = true; the general form on int16 rows: NT = 1 or 2, BOX = false);
+//   the family F (sg_2d_st16.hpp) and TOUT, what roll_item stores through (h16: bytes; i16: short or float);
 //   job (Job2DSt16<F>), taps, strips, bands, total_items, aligned: the kernel's arguments.
     typedef Roll<N> R;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *mine = lds + wv * (2 * 2 * R::BUFW);              // two LDS rows per term, private to this wave
+    float *mine = lds + wv * (2 * NT * R::BUFW);             // two LDS rows per term, private to this wave
 
     // the fp32 tile's block order: bits 8.. of `aligned` = blocks per XCD chunk, 0 = every XCD sweeps one contiguous eighth of the launch
     const unsigned nblk = gridDim.x;
@@ -39,6 +40,6 @@
     // interior strips: all 256 input columns inside the frame, all SW output columns stored.  The host sends only frames whose every strip can run on
     // vector loads (frame_plan_h16), so the edge strips take the remapped quads: MODE 2 (padded modes) or 3 (VALID: partial quads).
     if (sx - 4 * R::HL >= 0 && sx - 4 * R::HL + 256 <= job.cols && sx >= xlo && sx + R::SW <= xhi)
-        roll_item<N, 2, 1, 1, true, false, TR>(job, taps, mine, in, outs, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);
-    else if (valid) roll_item<N, 2, 1, 3, true, false, TR>(job, taps, mine, in, outs, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);
-    else roll_item<N, 2, 1, 2, true, false, TR>(job, taps, mine, in, outs, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);
+        roll_item<N, NT, 1, 1, BOX, false, TR>(job, taps, mine, in, outs, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);
+    else if (valid) roll_item<N, NT, 1, 3, BOX, false, TR>(job, taps, mine, in, outs, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);
+    else roll_item<N, NT, 1, 2, BOX, false, TR>(job, taps, mine, in, outs, sx - 4 * R::HL, yb, nout, lane, xlo, xhi, ylo, yhi);

@@ -113,6 +113,37 @@ inline bool roll16_fp32_takes_tiles(int n, int terms, const float *factors, floa
     return sg2d_launch_rolling_st16<H16Family2D>(n, terms, nullptr, factors, scale, 0, nullptr) == 0;
 }
 
+// ---- savgol2d_gradient_batch_i16's DIRECT route (sg_2d_grad16_host.hpp): the two kernels the fp32 gradient runs on a square window up to n = 7, on int16 rows.
+// Each launcher: 0 = launched, 1 = not covered (another group's half window, factors the fp32 launcher would not take this way, SAVGOL_HIP_ROLL_TILE=0:
+// nothing has been enqueued), -1 = error.  The caller has checked frame_plan_h16's layout conditions.
+// gy -- sg_2d_roll.hip built with SG_ROLL_I16_GEN (Makefile, ROLL_GEN16_RULE): sg2d_rolling_gen_i16_kernel<N, NT, OUT_F32>, the general one- and two-term
+// 20-row tile with the taps of the fp32 launcher's own fill_taps.  job == NULL: the same answer with nothing launched (the route rule's gy_direct).
+using RollGen16Launch = int(int n, int terms, const Job2DI16 *job, const float *factors, float scale, unsigned images, hipStream_t st);
+RollGen16Launch sg2d_launch_rolling_gen_i16_g0, sg2d_launch_rolling_gen_i16_g1, sg2d_launch_rolling_gen_i16_g2, sg2d_launch_rolling_gen_i16_g3;
+inline int sg2d_launch_rolling_gen_i16(int n, int terms, const Job2DI16 *job, const float *factors, float scale, unsigned images, hipStream_t st)
+{
+    static constexpr RollGen16Launch *groups[] = {sg2d_launch_rolling_gen_i16_g0, sg2d_launch_rolling_gen_i16_g1, sg2d_launch_rolling_gen_i16_g2, sg2d_launch_rolling_gen_i16_g3};
+    for (auto group : groups) {
+        const int rc = group(n, terms, job, factors, scale, images, st);
+        if (rc != 1) return rc;
+    }
+    return 1;
+}
+// gx -- sg_2d_hf.hip built with SG_HF_I16 (Makefile, HF_I16_RULE): sg2d_rolling_hf_i16_kernel<N, NT, OUT_F32>, one term or two of one x parity in ONE
+// launch, never accumulating; sigma / sigma2 as for sg2d_launch_rolling_hf (sg_2d.hpp).
+using HfI16Launch = int(int n, const Job2DI16 &job, const float *factors, float scale, float sigma, const float *factors2, float sigma2, unsigned images, int cu_count, hipStream_t st);
+HfI16Launch sg2d_launch_rolling_hf_i16_g0, sg2d_launch_rolling_hf_i16_g1, sg2d_launch_rolling_hf_i16_g2, sg2d_launch_rolling_hf_i16_g3;
+inline int sg2d_launch_rolling_hf_i16(int n, const Job2DI16 &job, const float *factors, float scale, float sigma, const float *factors2, float sigma2, unsigned images,
+                                      int cu_count, hipStream_t st)
+{
+    static constexpr HfI16Launch *groups[] = {sg2d_launch_rolling_hf_i16_g0, sg2d_launch_rolling_hf_i16_g1, sg2d_launch_rolling_hf_i16_g2, sg2d_launch_rolling_hf_i16_g3};
+    for (auto group : groups) {
+        const int rc = group(n, job, factors, scale, sigma, factors2, sigma2, images, cu_count, st);
+        if (rc != 1) return rc;
+    }
+    return 1;
+}
+
 // sg_2d_st16.hip: the staged route's two launchers, instantiated for both families.  `frames` frames of rows x cols; the fp32 side is library scratch:
 // 16-byte aligned, row stride FrameStageH16::stride (cols rounded up to 4), frames back to back.
 // 16-bit frames of in_type (any base, stride, pitch) -> scratch, widened exactly; the pad columns cols .. stride - 1 are zeroed (nothing reads them)
