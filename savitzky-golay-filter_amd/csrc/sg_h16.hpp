@@ -1,4 +1,4 @@
-// sg_h16.hpp -- fp16 / bf16 elements <-> fp32, for every kernel on 16-bit float storage (sg_k1d_st16.hpp, sg_stream_dma_h16.hip, sg_stream.hip): the
+// sg_h16.hpp -- fp16 / bf16 elements <-> fp32, for every kernel on 16-bit float storage (sg_k1d_st16.hpp, sg_stream_dma_st16.hip, sg_stream.hip): the
 // tree's one definition.  Widening is exact (fp16 subnormals included: the hardware convert with the kernels' default denormal mode), narrowing rounds
 // once to nearest even (NaN stays NaN, overflow into fp16 gives +-Inf).  Where the storage type is an argument it is wave-uniform.
 #pragma once

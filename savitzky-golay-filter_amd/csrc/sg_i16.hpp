@@ -1,4 +1,4 @@
-// sg_i16.hpp -- int16 elements <-> fp32, for every kernel on int16 storage (sg_k1d_st16.hpp, sg_stream_dma_i16.hip, sg_stream.hip): the tree's one
+// sg_i16.hpp -- int16 elements <-> fp32, for every kernel on int16 storage (sg_k1d_st16.hpp, sg_stream_dma_st16.hip, sg_stream.hip): the tree's one
 // definition.  Widening is the exact sign-extending convert; narrowing converts ONCE: round to nearest with ties to even, saturate to
 // [-32768, 32767] (so +-Inf saturate), NaN gives 0 -- the contract of the int16 calls (include/savgol_hip.h).
 #pragma once

@@ -26,6 +26,7 @@
 // One kernel per half window serves every type pair of its family.
 #pragma once
 
+#include "sg_family.hpp"
 #include "sg_h16.hpp"
 #include "sg_i16.hpp"
 #include "sg_k1d.hpp"
@@ -167,13 +168,10 @@ __global__ __launch_bounds__(64 * SG_K1D_WAVES, (K1D<float, N, VPL_NARROW>::MIN_
 }
 
 // The instantiation files (sg_k1d_st16.hip, sg_k1d_st16_momenth.hip, sg_k1d_multi_st16.hip) are compiled once per family, -DSG_FAMILY=h16|i16:
-// `Family` is that family's policy, SG_FAMILY_NAME(sg1d_, _kernel) its entry point sg1d_h16_kernel / sg1d_i16_kernel.
+// `Family` is that family's policy, SG_FAMILY_NAME(sg1d_, _kernel) (sg_family.hpp) its entry point sg1d_h16_kernel / sg1d_i16_kernel.
 #ifdef SG_FAMILY
 struct Families { typedef H16Family h16; typedef I16Family i16; };
 typedef Families::SG_FAMILY Family;
-#define SG_CAT3_(a, b, c) a##b##c
-#define SG_CAT3(a, b, c) SG_CAT3_(a, b, c)
-#define SG_FAMILY_NAME(pre, post) SG_CAT3(pre, SG_FAMILY, post)
 #endif
 
 }  // namespace sg

@@ -33,12 +33,9 @@
 #include "sg_h16.hpp"
 #include "sg_i16.hpp"
 #include "sg_stream.hpp"
-#include "sg_stream_h16.hpp"
-#include "sg_stream_i16.hpp"
 #include "sg_stream_multi.hpp"
-#include "sg_stream_multi_h16.hpp"
-#include "sg_stream_multi_i16.hpp"
 #include "sg_stream_roll.hpp"
+#include "sg_stream_st16.hpp"
 
 extern "C" int sg_small_stream_rows(void *ctx, const float *d_table, const float *ring, int ws, int wp, float dt_inv, int count, const int *row,
                                     const int *backward, float *output);
@@ -830,87 +827,83 @@ size_t h16_elem(int t) { return t == SAVGOL_HIP_F32 ? 4 : 2; }         // bytes 
 bool stream_dma_switch() { static const int v = [] { const char *e = getenv("SAVGOL_HIP_STREAM_DMA"); return e ? atoi(e) : 1; }(); return v != 0; }
 bool stream_moment_switch() { static const int v = [] { const char *e = getenv("SAVGOL_HIP_STREAM_MOMENT"); return e ? atoi(e) : 1; }(); return v != 0; }
 
-void h16_widen(const unsigned short *in, float *out, size_t count, bool bf, hipStream_t st)
-{
-    hipLaunchKernelGGL(sg::sg_h16_widen_kernel, dim3((unsigned)((count + 1023) / 1024)), dim3(256), 0, st, in, out, count, bf ? 1 : 0);
-}
-// rows [first_row, rows) of `in` (fp32, pitch streams) -> the same rows of `out`
-void h16_round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, int out_type, hipStream_t st)
+// rows [first_row, rows) of `in` (fp32, pitch streams) -> the same rows of `out` through a family's round kernel; `arg`: the kernel's last argument
+template <class Kernel>
+void round_rows(Kernel kernel, const float *in, void *out, size_t streams, size_t first_row, size_t rows, int arg, hipStream_t st)
 {
     const size_t lo = first_row * streams, hi = rows * streams;
     if (lo >= hi) return;
     const size_t groups = (hi - (lo & ~(size_t)3) + 3) / 4;
-    hipLaunchKernelGGL(sg::sg_h16_round_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, in, out, lo, hi, out_type);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, in, out, lo, hi, arg);
 }
 
-void i16_widen(const short *in, float *out, size_t count, hipStream_t st)
-{
-    hipLaunchKernelGGL(sg::sg_i16_widen_kernel, dim3((unsigned)((count + 1023) / 1024)), dim3(256), 0, st, in, out, count);
-}
-void i16_round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, int out_type, hipStream_t st)
-{
-    const size_t lo = first_row * streams, hi = rows * streams;
-    if (lo >= hi) return;
-    const size_t groups = (hi - (lo & ~(size_t)3) + 3) / 4;
-    hipLaunchKernelGGL(sg::sg_i16_round_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, in, out, lo, hi, out_type == SAVGOL_HIP_F32 ? 1 : 0);
-}
-
-// What the two calls differ in, the storage of the samples and of the outputs: the call's name, the type check and its text, the element sizes, the
-// widen, round and tail-store launchers, and the three launchers of the body tile.  The job is BankJobH16 for both (16-bit words either way).
-struct BlockH16 {
-    typedef unsigned short Sample;
-    static constexpr const char *who = "savgol_streambank_push_block_h16", *launch_who = "savgol_streambank_push_block_h16 launch";
+// What the two storages of the samples and of the outputs differ in, for the single call (block16_push) and the fused one (Fused16 below): the single
+// call's name, the type check and its text, the widen, round and tail-store launches, the launchers of the body tiles, the fused call's plan and the
+// single call itself.  The jobs are BankJobH16 and BankJobMultiH16 for both (16-bit words either way).
+struct StoreH16 {
+    typedef sg::H16StreamFamily::Sample Sample;
+    static constexpr const char *block_who = "savgol_streambank_push_block_h16", *block_launch_who = "savgol_streambank_push_block_h16 launch";
     int in_type, out_type;
-    bool types_ok() const
+    bool types_ok(const char *who) const
     {
         if ((in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16) && (out_type == in_type || out_type == SAVGOL_HIP_F32)) return true;
         sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who,
                      h16_type_name(in_type), h16_type_name(out_type), in_type, out_type);
         return false;
     }
-    size_t out_elem() const { return h16_elem(out_type); }
-    void widen(const Sample *in, float *out, size_t count, hipStream_t st) const { h16_widen(in, out, count, in_type == SAVGOL_HIP_BF16, st); }
-    void round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { h16_round(in, out, streams, first_row, rows, out_type, st); }
+    void widen(const Sample *in, float *out, size_t count, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(sg::sg_h16_widen_kernel, dim3((unsigned)((count + 1023) / 1024)), dim3(256), 0, st, in, out, count, in_type == SAVGOL_HIP_BF16 ? 1 : 0);
+    }
+    void round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const
+    {
+        round_rows(sg::sg_h16_round_kernel, in, out, streams, first_row, rows, out_type, st);
+    }
     void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t ticks, hipStream_t st) const
     {
         hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
                            b->filter->window_size, b->wp, ticks, in_type == SAVGOL_HIP_BF16 ? 1 : 0);
     }
-    int launch_mom(int n, const sg::StreamMomentFit &fit, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
+    static constexpr auto launch_mom = sg::sg_bank_dma_h16_launch_mom;
+    static constexpr auto launch_lo = sg::sg_bank_dma_h16_launch_lo, launch_hi = sg::sg_bank_dma_h16_launch_hi;
+    static constexpr auto launch_multi_fma = sg::sg_bank_dma_multi_h16_launch_fma, launch_multi_ref = sg::sg_bank_dma_multi_h16_launch_ref;
+    template <class... A> static sg::MultiPlan multi_plan(A &&...a) { return sg::block_plan_multi_h16(static_cast<A &&>(a)...); }
+    int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, void *out, void *stream) const
     {
-        return sg::sg_bank_dma_h16_launch_mom(n, fit, center, job, geo, grid, st);
-    }
-    int launch_taps(int n, int fma, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
-    {
-        return (n <= 16 ? sg::sg_bank_dma_h16_launch_lo : sg::sg_bank_dma_h16_launch_hi)(n, fma, center, job, geo, grid, st);
+        return savgol_streambank_push_block_h16(b, samples, in_type, ticks, out, out_type, stream);
     }
 };
-struct BlockI16 {
-    typedef short Sample;
-    static constexpr const char *who = "savgol_streambank_push_block_i16", *launch_who = "savgol_streambank_push_block_i16 launch";
+struct StoreI16 {
+    typedef sg::I16StreamFamily::Sample Sample;
+    static constexpr const char *block_who = "savgol_streambank_push_block_i16", *block_launch_who = "savgol_streambank_push_block_i16 launch";
     static constexpr int in_type = SAVGOL_HIP_I16;
     int out_type;
-    bool types_ok() const
+    bool types_ok(const char *who) const
     {
         if (out_type == SAVGOL_HIP_I16 || out_type == SAVGOL_HIP_F32) return true;
         sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, h16_type_name(out_type), out_type);
         return false;
     }
-    size_t out_elem() const { return out_type == SAVGOL_HIP_F32 ? 4 : 2; }
-    void widen(const Sample *in, float *out, size_t count, hipStream_t st) const { i16_widen(in, out, count, st); }
-    void round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { i16_round(in, out, streams, first_row, rows, out_type, st); }
+    void widen(const Sample *in, float *out, size_t count, hipStream_t st) const
+    {
+        hipLaunchKernelGGL(sg::sg_i16_widen_kernel, dim3((unsigned)((count + 1023) / 1024)), dim3(256), 0, st, in, out, count);
+    }
+    void round(const float *in, void *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const
+    {
+        round_rows(sg::sg_i16_round_kernel, in, out, streams, first_row, rows, out_type == SAVGOL_HIP_F32 ? 1 : 0, st);
+    }
     void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t ticks, hipStream_t st) const
     {
         hipLaunchKernelGGL(sg::sg_bank_store_tail_i16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
                            b->filter->window_size, b->wp, ticks);
     }
-    int launch_mom(int n, const sg::StreamMomentFit &fit, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
+    static constexpr auto launch_mom = sg::sg_bank_dma_i16_launch_mom;
+    static constexpr auto launch_lo = sg::sg_bank_dma_i16_launch_lo, launch_hi = sg::sg_bank_dma_i16_launch_hi;
+    static constexpr auto launch_multi_fma = sg::sg_bank_dma_multi_i16_launch_fma, launch_multi_ref = sg::sg_bank_dma_multi_i16_launch_ref;
+    template <class... A> static sg::MultiPlan multi_plan(A &&...a) { return sg::block_plan_multi_i16(static_cast<A &&>(a)...); }
+    int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, void *out, void *stream) const
     {
-        return sg::sg_bank_dma_i16_launch_mom(n, fit, center, job, geo, grid, st);
-    }
-    int launch_taps(int n, int fma, const float *center, const sg::BankJobH16 &job, const sg::TileGeom &geo, unsigned grid, hipStream_t st) const
-    {
-        return (n <= 16 ? sg::sg_bank_dma_i16_launch_lo : sg::sg_bank_dma_i16_launch_hi)(n, fma, center, job, geo, grid, st);
+        return savgol_streambank_push_block_i16(b, samples, ticks, out, out_type, stream);
     }
 };
 
@@ -921,10 +914,10 @@ int block16_staged(const S &store, SavgolStreamBank *bank, sg::DeviceCtx *ctx, c
 {
     const size_t streams = bank->streams, chunk = sg::h16_staged_chunk(streams, ticks);
     const size_t frame = (chunk * streams * sizeof(float) + 255) & ~(size_t)255;
-    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, S::who));
+    char *scratch = static_cast<char *>(sg::scratch_alloc(ctx, 2 * frame, st, S::block_who));
     if (!scratch) return -1;
     float *sin = reinterpret_cast<float *>(scratch), *sout = reinterpret_cast<float *>(scratch + frame);
-    const size_t out_elem = store.out_elem();
+    const size_t out_elem = h16_elem(store.out_type);
     long long produced = 0;
     int rc = 0;
     for (size_t done = 0; done < ticks && rc >= 0; done += chunk) {
@@ -935,9 +928,9 @@ int block16_staged(const S &store, SavgolStreamBank *bank, sg::DeviceCtx *ctx, c
         store.round(sout, static_cast<char *>(d_out) + done * streams * out_elem, streams, part - (size_t)rc, part, st);
         produced += rc;
     }
-    const bool freed = sg::scratch_free(scratch, st, S::who);
+    const bool freed = sg::scratch_free(scratch, st, S::block_who);
     if (rc < 0 || !freed) return -1;
-    if (!sg::hip_ok(hipGetLastError(), S::launch_who)) return -1;
+    if (!sg::hip_ok(hipGetLastError(), S::block_launch_who)) return -1;
     return (int)produced;
 }
 
@@ -946,9 +939,9 @@ int block16_staged(const S &store, SavgolStreamBank *bank, sg::DeviceCtx *ctx, c
 template <class S>
 int block16_push(const S &store, SavgolStreamBank *bank, const void *d_samples, size_t ticks, void *d_out, void *stream)
 {
-    const char *const who = S::who;
+    const char *const who = S::block_who;
     if (!bank || !d_samples || !d_out) { sg_set_error("%s: NULL pointer", who); return -1; }
-    if (!store.types_ok()) return -1;
+    if (!store.types_ok(who)) return -1;
     if (!sg::bank_on_current_device(bank, who)) return -1;              // the tick service running, or the bank on another device
     if (ticks == 0) return 0;
     if (ticks > ((size_t)1 << 30)) {
@@ -958,7 +951,7 @@ int block16_push(const S &store, SavgolStreamBank *bank, const void *d_samples, 
     const size_t streams = bank->streams;
     {
         // not in place, like the fp32 call; compared byte-wise, the element sizes may differ
-        const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * store.out_elem();
+        const unsigned long long in_bytes = (unsigned long long)ticks * streams * 2, out_bytes = (unsigned long long)ticks * streams * h16_elem(store.out_type);
         const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_samples), out0 = reinterpret_cast<uintptr_t>(d_out);
         if (in0 < out0 + out_bytes && out0 < in0 + in_bytes) {
             sg_set_error("%s: d_samples and d_out overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of outputs may not share a byte)",
@@ -1005,20 +998,20 @@ int block16_push(const S &store, SavgolStreamBank *bank, const void *d_samples, 
         job.samples = reinterpret_cast<const unsigned short *>(samples); job.out[0] = d_out; job.streams = streams; job.ticks = ticks; job.band0 = (unsigned)(head / 32);
         job.dt_inv[0] = bank->dt_inv; job.centre_sum[0] = (float)wsum; job.centre[0] = centre ? 1 : 0;
         job.in_type = (unsigned)store.in_type; job.out_type = (unsigned)store.out_type;
-        if (plan.form == sg::MOMENT_TILES) covered = store.launch_mom(n, fit, weights, job, plan.geo, plan.grid, st);
-        else covered = store.launch_taps(n, fma ? 1 : 0, weights, job, plan.geo, plan.grid, st);
+        if (plan.form == sg::MOMENT_TILES) covered = S::launch_mom(n, fit, weights, job, plan.geo, plan.grid, st);
+        else covered = (n <= 16 ? S::launch_lo : S::launch_hi)(n, fma ? 1 : 0, weights, job, plan.geo, plan.grid, st);
     }
     if (covered != 0) {
         // the runtime refused the body's launch (nothing of the body is enqueued): the head becomes a finished block push of its own -- its newest
         // samples into the ring, the counters -- and the rest of the call takes the staged route
         store.store_tail(bank, samples, head, st);
         const int first = bank_advance(bank, head);
-        const int rest = block16_staged(store, bank, ctx, samples + head * streams, plan.body, static_cast<char *>(d_out) + head * streams * store.out_elem(), st);
+        const int rest = block16_staged(store, bank, ctx, samples + head * streams, plan.body, static_cast<char *>(d_out) + head * streams * h16_elem(store.out_type), st);
         return rest < 0 || !freed ? -1 : first + rest;
     }
     // the newest min(ticks, 2n + 1) samples, widened, into the ring; the counters once
     store.store_tail(bank, samples, ticks, st);
-    if (!freed || !sg::hip_ok(hipGetLastError(), S::launch_who)) return -1;
+    if (!freed || !sg::hip_ok(hipGetLastError(), S::block_launch_who)) return -1;
     return bank_advance(bank, ticks);
 }
 }  // namespace
@@ -1027,12 +1020,12 @@ extern "C" {
 
 int savgol_streambank_push_block_h16(SavgolStreamBank *bank, const void *d_samples, int in_type, size_t ticks, void *d_out, int out_type, void *stream)
 {
-    return block16_push(BlockH16{in_type, out_type}, bank, d_samples, ticks, d_out, stream);
+    return block16_push(StoreH16{in_type, out_type}, bank, d_samples, ticks, d_out, stream);
 }
 
 int savgol_streambank_push_block_i16(SavgolStreamBank *bank, const int16_t *d_samples, size_t ticks, void *d_out, int out_type, void *stream)
 {
-    return block16_push(BlockI16{out_type}, bank, d_samples, ticks, d_out, stream);
+    return block16_push(StoreI16{out_type}, bank, d_samples, ticks, d_out, stream);
 }
 
 }  // extern "C"
@@ -1046,7 +1039,7 @@ struct MultiCall {
 };
 
 // What the three fused calls differ in, the storage of the samples and of the outputs: the element types, the type-pair check, the texts of the overlap
-// refusals, the plan, the widening and the conversion of a staged head, the body's job and launchers, the tail store and the single call (SINGLE plans,
+// refusals, the plan, the widening and the conversion of a staged head (`widen`, `round`), the body's job and launchers, the tail store and the single call (SINGLE plans,
 // and the rest of a partly refused call).
 struct FusedF32 {
     typedef float Sample;
@@ -1076,59 +1069,12 @@ struct FusedF32 {
     }
     int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, Out *out, void *stream) const { return savgol_streambank_push_block(b, samples, ticks, out, stream); }
 };
-struct FusedH16 {
-    typedef unsigned short Sample;
-    typedef void Out;
-    typedef sg::BankJobMultiH16 Job;
-    static constexpr bool staged_head = true;                // the heads run on the head's rows widened into fp32 scratch, and are rounded out
-    int in_type, out_type;
-    bool types_ok(const char *who) const
-    {
-        if ((in_type == SAVGOL_HIP_F16 || in_type == SAVGOL_HIP_BF16) && (out_type == in_type || out_type == SAVGOL_HIP_F32)) return true;
-        sg_set_error("%s: type pair %s -> %s (%d -> %d) is not served: f16 -> f16, bf16 -> bf16, f16 -> f32, bf16 -> f32 are", who,
-                     h16_type_name(in_type), h16_type_name(out_type), in_type, out_type);
-        return false;
-    }
-    void samples_overlap(const char *who, int k, unsigned long long in_bytes, unsigned long long out_bytes) const
-    {
-        sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of an output may not share a byte)",
-                     who, k, in_bytes, out_bytes);
-    }
-    void outputs_overlap(const char *who, int j, int k, unsigned long long out_bytes) const
-    {
-        sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes %llu bytes of its own)", who, j, k, out_bytes);
-    }
-    template <class... A> static sg::MultiPlan plan(A &&...a) { return sg::block_plan_multi_h16(static_cast<A &&>(a)...); }
-    void types_into(Job *job) const { job->in_type = (unsigned)in_type; job->out_type = (unsigned)out_type; }
-    void widen_head(const Sample *in, float *out, size_t count, hipStream_t st) const { h16_widen(in, out, count, in_type == SAVGOL_HIP_BF16, st); }
-    void round_head(const float *in, Out *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { h16_round(in, out, streams, first_row, rows, out_type, st); }
-    int launch(bool fma, int n, int per, const float *const *center, const Job &job, const sg::MultiPlan &plan, hipStream_t st) const
-    {
-        return (fma ? sg::sg_bank_dma_multi_h16_launch_fma : sg::sg_bank_dma_multi_h16_launch_ref)(n, per, center, job, plan, st);
-    }
-    void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t done, hipStream_t st) const
-    {
-        hipLaunchKernelGGL(sg::sg_bank_store_tail_h16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
-                           b->filter->window_size, b->wp, done, in_type == SAVGOL_HIP_BF16 ? 1 : 0);
-    }
-    int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, Out *out, void *stream) const
-    {
-        return savgol_streambank_push_block_h16(b, samples, in_type, ticks, out, out_type, stream);
-    }
-};
-struct FusedI16 {
-    typedef short Sample;
+// both 16-bit storages: the single call's storage policy plus the fused call's own
+template <class St>
+struct Fused16 : St {
     typedef void Out;
     typedef sg::BankJobMultiH16 Job;                         // its samples are 16-bit words either way
-    static constexpr bool staged_head = true;                // as FusedH16: widened into fp32 scratch, converted out
-    static constexpr int  in_type = SAVGOL_HIP_I16;
-    int out_type;
-    bool types_ok(const char *who) const
-    {
-        if (out_type == SAVGOL_HIP_I16 || out_type == SAVGOL_HIP_F32) return true;
-        sg_set_error("%s: output type %s (%d) is not served (i16 -> i16, i16 -> f32)", who, h16_type_name(out_type), out_type);
-        return false;
-    }
+    static constexpr bool staged_head = true;                // the heads run on the head's rows widened into fp32 scratch, and are converted out
     void samples_overlap(const char *who, int k, unsigned long long in_bytes, unsigned long long out_bytes) const
     {
         sg_set_error("%s: d_samples and d_outs[%d] overlap (the block push does not run in place: the %llu bytes of samples and the %llu bytes of an output may not share a byte)",
@@ -1138,24 +1084,15 @@ struct FusedI16 {
     {
         sg_set_error("%s: d_outs[%d] and d_outs[%d] overlap (every bank writes %llu bytes of its own)", who, j, k, out_bytes);
     }
-    template <class... A> static sg::MultiPlan plan(A &&...a) { return sg::block_plan_multi_i16(static_cast<A &&>(a)...); }
-    void types_into(Job *job) const { job->in_type = (unsigned)in_type; job->out_type = (unsigned)out_type; }
-    void widen_head(const Sample *in, float *out, size_t count, hipStream_t st) const { i16_widen(in, out, count, st); }
-    void round_head(const float *in, Out *out, size_t streams, size_t first_row, size_t rows, hipStream_t st) const { i16_round(in, out, streams, first_row, rows, out_type, st); }
+    template <class... A> static sg::MultiPlan plan(A &&...a) { return St::multi_plan(static_cast<A &&>(a)...); }
+    void types_into(Job *job) const { job->in_type = (unsigned)this->in_type; job->out_type = (unsigned)this->out_type; }
     int launch(bool fma, int n, int per, const float *const *center, const Job &job, const sg::MultiPlan &plan, hipStream_t st) const
     {
-        return (fma ? sg::sg_bank_dma_multi_i16_launch_fma : sg::sg_bank_dma_multi_i16_launch_ref)(n, per, center, job, plan, st);
-    }
-    void store_tail(const SavgolStreamBank *b, const Sample *samples, size_t done, hipStream_t st) const
-    {
-        hipLaunchKernelGGL(sg::sg_bank_store_tail_i16_kernel, dim3((unsigned)((b->streams + 255) / 256), 8), dim3(256), 0, st, b->d_ring, samples, b->streams,
-                           b->filter->window_size, b->wp, done);
-    }
-    int single(SavgolStreamBank *b, const Sample *samples, size_t ticks, Out *out, void *stream) const
-    {
-        return savgol_streambank_push_block_i16(b, samples, ticks, out, out_type, stream);
+        return (fma ? St::launch_multi_fma : St::launch_multi_ref)(n, per, center, job, plan, st);
     }
 };
+typedef Fused16<StoreH16> FusedH16;
+typedef Fused16<StoreI16> FusedI16;
 
 // every refusal of the call and of its route query, in the header's order, then the plan; false = refused (text set), nothing enqueued or changed
 template <class S>
@@ -1263,7 +1200,7 @@ int fused_push(const S &store, const char *who, SavgolStreamBank *const *banks, 
         if (!scratch) return -1;
         head_in = reinterpret_cast<float *>(scratch);
         head_out = reinterpret_cast<float *>(scratch + frame);
-        store.widen_head(d_samples, reinterpret_cast<float *>(scratch), head * streams, st);
+        store.widen(d_samples, reinterpret_cast<float *>(scratch), head * streams, st);
     } else {
         head_in = d_samples;
     }
@@ -1280,7 +1217,7 @@ int fused_push(const S &store, const char *who, SavgolStreamBank *const *banks, 
         if constexpr (S::staged_head) {
             const unsigned long long ws = (unsigned long long)b->filter->window_size;
             const size_t silent = b->received + 1 >= ws ? 0 : (size_t)(ws - 1 - b->received);     // head ticks without an output (<= 2n <= 64)
-            store.round_head(head_out, d_outs[k], streams, silent, head, st);
+            store.round(head_out, d_outs[k], streams, silent, head, st);
         }
     }
     const bool freed = !scratch || sg::scratch_free(scratch, st, who);
@@ -1345,26 +1282,26 @@ int savgol_streambank_push_block_multi(SavgolStreamBank *const *banks, int count
 int savgol_streambank_push_block_multi_h16_route(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
                                                  void *const *d_outs, int out_type)
 {
-    return fused_route(FusedH16{in_type, out_type}, "savgol_streambank_push_block_multi_h16_route", banks, count, static_cast<const unsigned short *>(d_samples), ticks,
+    return fused_route(FusedH16{{in_type, out_type}}, "savgol_streambank_push_block_multi_h16_route", banks, count, static_cast<const unsigned short *>(d_samples), ticks,
                        d_outs);
 }
 
 int savgol_streambank_push_block_multi_h16(SavgolStreamBank *const *banks, int count, const void *d_samples, int in_type, size_t ticks,
                                            void *const *d_outs, int out_type, int *produced, void *stream)
 {
-    return fused_push(FusedH16{in_type, out_type}, "savgol_streambank_push_block_multi_h16", banks, count, static_cast<const unsigned short *>(d_samples), ticks,
+    return fused_push(FusedH16{{in_type, out_type}}, "savgol_streambank_push_block_multi_h16", banks, count, static_cast<const unsigned short *>(d_samples), ticks,
                       d_outs, produced, stream);
 }
 
 int savgol_streambank_push_block_multi_i16_route(SavgolStreamBank *const *banks, int count, const int16_t *d_samples, size_t ticks, void *const *d_outs, int out_type)
 {
-    return fused_route(FusedI16{out_type}, "savgol_streambank_push_block_multi_i16_route", banks, count, d_samples, ticks, d_outs);
+    return fused_route(FusedI16{{out_type}}, "savgol_streambank_push_block_multi_i16_route", banks, count, d_samples, ticks, d_outs);
 }
 
 int savgol_streambank_push_block_multi_i16(SavgolStreamBank *const *banks, int count, const int16_t *d_samples, size_t ticks, void *const *d_outs, int out_type,
                                            int *produced, void *stream)
 {
-    return fused_push(FusedI16{out_type}, "savgol_streambank_push_block_multi_i16", banks, count, d_samples, ticks, d_outs, produced, stream);
+    return fused_push(FusedI16{{out_type}}, "savgol_streambank_push_block_multi_i16", banks, count, d_samples, ticks, d_outs, produced, stream);
 }
 
 static int bank_edge_rows(SavgolStreamBank *bank, float *d_out, int max_rows, void *stream, bool leading, const char *who)

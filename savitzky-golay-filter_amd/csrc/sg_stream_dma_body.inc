@@ -1,10 +1,10 @@
 // sg_stream_dma_body.inc -- the BODY tile of the stream block push, once: the LDS-DMA tile of bands >= 2 of a call on 16-bit rows, with K >= 1 outputs
 // from one trip of each row through the wave's LDS ring.  A FRAGMENT, as sg_stream_dma_feed.hpp is: the statements of a kernel, included as the whole body
-// of sg_bank_dma_h16_kernel (K = 1; sg_stream_dma_h16.hip) and of sg_bank_dma_multi_h16_kernel (K = 2, 3; sg_stream_dma_multi_h16.hip).  Not a function
+// of sg_bank_dma_{h16,i16}_kernel (K = 1; sg_stream_dma_st16.hip) and of sg_bank_dma_multi_{h16,i16}_kernel (K = 2, 3; sg_stream_dma_multi_st16.hip).  Not a function
 // template: hipcc optimises a __device__ function on its own before it inlines it, with the job behind a pointer, and the kernels then come out with
 // commuted address arithmetic and other registers (745 of 5177 instructions at n = 2, three outputs); included, every kernel compiles the tokens it
 // always did (profiles/stream_body_isa_diff.txt: every kernel reads `same`).  The including scope provides
-//   constexpr int N, K, TRT, WPB, DP, FCH, MOM; constexpr bool FMA;
+//   constexpr int N, K, TRT, WPB, DP, FCH, MOM; constexpr bool FMA; F (the storage family: H16StreamFamily or I16StreamFamily, sg_stream_st16.hpp);
 //   job (BankJobH16 or BankJobMultiH16: the same fields, the per-output ones arrays), all (the taps: body_taps, sg_stream_dma_body.hpp), geo (TileGeom).
 // DP: the ring, in DMAs = KiB = four rows each.
 //
@@ -22,11 +22,10 @@
 //   * a finished output row issues K stores (DmaQueue<N, 32, DP, 4, K>, sg_stream_host.hpp; tests/mock/dma_queue_multi_h16.cpp): 16 -> 16 bit rounds the
 //     pair once to nearest even into one dword, 16 bit -> fp32 keeps the fp32 store; range-checked descriptors, nontemporal like the fp32 tile's.
 // The block-moment form (MOM > 0) is the single call's (K = 1) alone.
-// STORAGE, a compile-time switch of the including file: with SG_BODY_I16 defined before the #include the 16-bit rows are int16 (sg_bank_dma_i16_kernel,
-// sg_stream_dma_i16.hip; sg_i16.hpp) -- the widen is the exact sign-extending convert of the dword's two halves and a 16-bit output row is rounded to
-// nearest even, saturated and packed once (NaN gives 0); in_type / out_type then only tell a 16-bit output row from an fp32 one, and the output step asks for
-// the 16-bit store first (the same two stores, one per output row).  Without it the three places below read what they always did: fp16 / bf16 by the
-// job's wave-uniform types (sg_h16.hpp).
+// STORAGE is the family F's: its widen2 and narrow2 are the converts of the three places below that know the element type.  h16 (sg_h16.hpp): fp16 /
+// bf16 by the job's wave-uniform types.  i16 (sg_i16.hpp): the widen is the exact sign-extending convert of the dword's two halves and a 16-bit output
+// row is rounded to nearest even, saturated and packed once (NaN gives 0); in_type / out_type then only tell a 16-bit output row from an fp32 one, and
+// the output step asks for the 16-bit store first (F::STORE16_FIRST: the same two stores, one per output row).
     typedef DmaQueue<N, TRT, DP, 4, K> Q;
     constexpr int TR = TRT, ROWS = TR + 2 * N, NI = Q::NI, RB = 256, RING = DP * 1024;
     static_assert(DP >= 2 && DP <= NI, "ring of row quads; the first eight rows are in it together");
@@ -92,25 +91,24 @@
             const f32x2 y = (MOM > 0 || FMA) ? __builtin_elementwise_fma(a, f32x2{job.dt_inv[k], job.dt_inv[k]}, backdts[k]) : a * f32x2{job.dt_inv[k], job.dt_inv[k]};
             const size_t orow = (size_t)(has_out ? tt : 0) * job.streams;
             // one store per output and output row whatever the type (the queue arithmetic is static); a row past the call stores into an empty descriptor
-#ifdef SG_BODY_I16
-            // the same two stores with the 16-bit one asked for first: in that order the int16 narrow (two temporaries where the bf16 convert needs one)
-            // does not sit at the tile's register peak (DESIGN 4.3f)
-            if (!of32) {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 2) : 0, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b32(narrow2_i16(y), rs, (int)(voff * 2u), 0, 2);
+            // (the family's order: with STORE16_FIRST the 16-bit store is asked for first -- the same two stores, written out: behind a lambda they schedule differently)
+            if constexpr (F::STORE16_FIRST) {
+                if (!of32) {
+                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 2) : 0, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b32(F::narrow2(y, obf), rs, (int)(voff * 2u), 0, 2);
+                } else {
+                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<float *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 4) : 0, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)(voff * 4u), 0, 2);
+                }
             } else {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<float *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 4) : 0, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)(voff * 4u), 0, 2);
+                if (of32) {
+                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<float *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 4) : 0, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)(voff * 4u), 0, 2);
+                } else {
+                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 2) : 0, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b32(F::narrow2(y, obf), rs, (int)(voff * 2u), 0, 2);
+                }
             }
-#else
-            if (of32) {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<float *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 4) : 0, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rs, (int)(voff * 4u), 0, 2);
-            } else {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned short *>(job.out[k]) + orow, 0, has_out ? (int)(job.streams * 2) : 0, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b32(narrow2(y, obf), rs, (int)(voff * 2u), 0, 2);
-            }
-#endif
         }
     };
     // the centre of the centred outputs: the sum of the tile's first eight widened rows (all real samples here), once, out of LDS after two DMAs have landed
@@ -120,11 +118,7 @@
         if (any) {
             f32x2 sum = f32x2{0.0f, 0.0f};
             wait_vm<(Q::younger(1, 0) > 63 ? 63 : Q::younger(1, 0))>();
-#ifdef SG_BODY_I16
-            static_for<8>([&](auto rc) -> bool { sum = sum + widen2_i16(row_in(rc)); return true; });
-#else
-            static_for<8>([&](auto rc) -> bool { sum = sum + widen2(row_in(rc), ibf); return true; });
-#endif
+            static_for<8>([&](auto rc) -> bool { sum = sum + F::widen2(row_in(rc), ibf); return true; });
             const f32x2 cen = centre_guard(sum);
             static_for<K>([&](auto kc) -> bool {
                 constexpr int k = decltype(kc)::value;
@@ -156,11 +150,7 @@
         auto take = [&](auto rc, const unsigned raw) {
             constexpr int r = decltype(rc)::value;
             if constexpr (r < ROWS) {                                                             // pad rows are never fed
-#ifdef SG_BODY_I16
-                const f32x2 wide = widen2_i16(raw);                                               // once per row, for every output
-#else
-                const f32x2 wide = widen2(raw, ibf);                                              // once per row, for every output
-#endif
+                const f32x2 wide = F::widen2(raw, ibf);                                           // once per row, for every output
                 static_for<K>([&](auto kc) -> bool {
                     if constexpr (MOM > 0 || FMA) feed(kc, rc, wide - cens[decltype(kc)::value]);
                     else feed(kc, rc, wide);

@@ -1,5 +1,5 @@
 // sg_stream_dma_feed.hpp -- ONE arriving row of an LDS-DMA stream tile goes into every accumulator it touches: the three summation forms (block moments,
-// the fused bank's chains, the reference's order) of sg_bank_dma_kernel (sg_stream_dma.hip) and sg_bank_dma_h16_kernel (sg_stream_dma_h16.hip).
+// the fused bank's chains, the reference's order) of sg_bank_dma_kernel (sg_stream_dma.hip) and the body tile (sg_stream_dma_body.inc).
 // A FRAGMENT, not a header of declarations: it is included inside the body of each kernel's `feed` lambda, so both kernels compile the same tokens and
 // the fp32 kernel compiles the tokens it always did (profiles/stream_h16_isa_diff.txt: every existing kernel reads `same`).  The including scope provides
 //   constexpr int N, TR, CH, MOM; constexpr bool FMA; constexpr int r (the slab row: tap r - m of output m);

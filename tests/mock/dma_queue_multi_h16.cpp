@@ -1,4 +1,4 @@
-// dma_queue_multi_h16.cpp -- tests/mock/dma_queue_multi.cpp for the fused multi-output stream tiles on 16-bit rows (csrc/sg_stream_dma_multi_h16.hip): a
+// dma_queue_multi_h16.cpp -- tests/mock/dma_queue_multi.cpp for the fused multi-output stream tiles on 16-bit rows (csrc/sg_stream_dma_multi_st16.hip): a
 // DMA moves FOUR rows of 256 bytes and a finished output row issues K stores.  Holds DmaQueue<N, 32, DP, 4, K> (csrc/sg_stream_host.hpp) to a simulation
 // of the wave's vector-memory queue: the DP DMAs of the prologue, then per step the K stores of every output row the step's four rows finish (pad rows of
 // an odd half window finish none) and the next DMA; at every wait the kernel issues -- the centre wait (the first eight rows = DMA 1), the first wait,

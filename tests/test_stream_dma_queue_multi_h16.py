@@ -1,4 +1,4 @@
-"""The s_waitcnt vmcnt counts of the fused multi-output stream tiles on 16-bit rows (csrc/sg_stream_dma_multi_h16.hip), held to a simulated queue on a CPU.
+"""The s_waitcnt vmcnt counts of the fused multi-output stream tiles on 16-bit rows (csrc/sg_stream_dma_multi_st16.hip), held to a simulated queue on a CPU.
 
 The kernel combines the 16-bit tile's four rows per DMA with the multi-output tile's K stores per finished output row: DmaQueue<N, 32, DP, 4, K>
 (csrc/sg_stream_host.hpp), a combination of template parameters no other kernel instantiates.  tests/mock/dma_queue_multi_h16.cpp issues what the kernel
